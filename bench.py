@@ -8,10 +8,14 @@ holds its own 100k-doc shard (weak scaling), every query is scored on every
 shard, and the per-shard top-1000 lists are all-gathered over RCCL and merged
 on the GPU.
 
-One JSON line on rank 0 (contract in the task statement), with a "roofline"
-object for the dominant kernel (HIP-event timed inside the library on the
-launching stream) and a "cpu_baseline" object (the oracle's C scorer on host
-cores, bounded sample, rank 0 at N=1 only).
+A plain run times the headline leg alone (encode_x3: the fp32-faithful bf16x3
+encode of configs[1]) and prints one JSON line on rank 0, with a "roofline" object
+for the dominant kernel (HIP-event timed inside the library on the launching
+stream, in the timed steps themselves).  --full adds every other leg (--legs picks
+among them), the oracle parity checks and the "cpu_baseline" objects (the oracle's
+C scorer / the fp32 PyTorch-CPU encoder on host cores, bounded sample, rank 0 at
+N=1 only).  --dump-outputs DIR writes the arrays the timed paths produced in their
+last step as DIR/<name>.npy (float32; same arguments -> same seeded inputs).
 """
 from __future__ import annotations
 
@@ -849,6 +853,39 @@ def text_legs(args):
     }
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(dirpath, rank, world, arrays):
+    """--dump-outputs: {name: array} -> DIR/<name>.npy in float32 (every value dumped is
+    an impact or an integer below 2^24: exact), `_rank<r>` appended at more than one
+    rank.  An array over its share of the 64 MB keeps a fixed seeded sample of its
+    elements (ascending flat indices, the same from run to run)."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1) // 4  # float32 elements per array
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(d / (name + ("" if world == 1 else f"_rank{rank}") + ".npy"), a)
+        log(f"[rank {rank}] dumped {name}: {a.shape}")
+
+
+def retrieve_lists(k, out_doc, out_score, out_n):
+    """The scorer's lists of the last step as (queries, k) arrays; the slots past a
+    query's count (never written) read -1."""
+    on = out_n.cpu().numpy()
+    valid = np.arange(k)[None, :] < on[:, None]
+    return {"retrieve_docs": np.where(valid, out_doc.cpu().numpy().reshape(-1, k), -1),
+            "retrieve_scores": np.where(valid, out_score.cpu().numpy().reshape(-1, k), -1),
+            "retrieve_counts": on}
+
+
+ALL_LEGS = "encode_x3,encode,encode_fp32,retrieve,retrieve_shard,text,index_e2e,rank_e2e"
+
+
 def _free_port():
     import socket
 
@@ -903,9 +940,15 @@ def main():
                     help="index_e2e leg: --process_batch_size (reference default 1600)")
     ap.add_argument("--text-docs", type=int, default=1_100_000,
                     help="text legs (quantize, index_create): docs of the impact TSV")
-    ap.add_argument("--legs", default="encode_x3,encode,encode_fp32,retrieve,retrieve_shard,text,"
-                                      "index_e2e,rank_e2e",
-                    help="encode_x3 (fp32-faithful bf16x3: the headline), encode (bf16 throughput "
+    ap.add_argument("--full", action="store_true",
+                    help="every leg of --legs, the oracle parity checks and the CPU baselines "
+                         "(a plain run times the headline leg, encode_x3, alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs of the timed legs "
+                         "as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--legs", default=None,
+                    help="legs of a --full run (default: " + ALL_LEGS + "): "
+                         "encode_x3 (fp32-faithful bf16x3: the headline), encode (bf16 throughput "
                          "mode), encode_fp32 (f32 MFMA: the exactness side leg, with the bf16x3 "
                          "flip rates against it), retrieve (100k-doc shard, configs[1]), "
                          "retrieve_shard (1.1M docs: "
@@ -914,6 +957,8 @@ def main():
                          "index_e2e (index.py's path end to end, tokenizer workers included), "
                          "rank_e2e (the rank CLI's path end to end on a 100k-doc index)")
     args = ap.parse_args()
+    if args.legs is not None and not args.full:
+        ap.error("--legs picks among the legs of a --full run: add --full")
 
     if args.gpus < 1:
         raise SystemExit(f"--gpus must be >= 1 (got {args.gpus})")
@@ -957,7 +1002,7 @@ def main():
     # and the merge would not be ordered after the scorer)
     main_stream = torch.cuda.Stream()
     torch.cuda.set_stream(main_stream)
-    legs = set(args.legs.split(","))
+    legs = set((args.legs or ALL_LEGS).split(",")) if args.full else {"encode_x3"}
     enc_res = ret_res = None
     x3_res = None
     if "encode_x3" in legs:
@@ -1078,7 +1123,7 @@ def main():
                     "launches_per_step": r["launches_per_step"], "roofline": r["roofline"]}
         if "exchange" in r:
             out[leg]["exchange"] = r["exchange"]
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         if x3_res is not None or enc_res is not None:
             cb = cpu_baseline_encode(args, *(x3_ctx if x3_res is not None else enc_ctx))
             out["cpu_baseline"] = cb
@@ -1087,6 +1132,18 @@ def main():
             out["retrieve"]["cpu_baseline"] = cb
             if x3_res is None and enc_res is None:
                 out["cpu_baseline"] = cb
+    if args.dump_outputs:
+        # (each encode leg's context ends with its output tensor: the term impacts)
+        arrays = {}
+        if x3_res is not None:
+            arrays["impacts_bf16x3"] = x3_ctx[-1].cpu().numpy()
+        if enc_res is not None:
+            arrays["impacts_bf16"] = enc_ctx[-1].cpu().numpy()
+        if f32_res is not None:
+            arrays["impacts_fp32"] = f32_ctx[-1].cpu().numpy()
+        if ret_res is not None:
+            arrays.update(retrieve_lists(args.k, *ret_ctx[4:]))
+        dump_outputs(args.dump_outputs, rank, world, arrays)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -18,12 +18,44 @@ def _run(code_or_args, env=None, timeout=120):
 def test_bench_refuses_world_size_gpus_mismatch():
     """A launcher's WORLD_SIZE that differs from --gpus exits non-zero before any GPU
     call (the driver would otherwise record n_gpus it did not ask for)."""
-    r = _run(["bench.py", "--gpus", "4", "--legs", "retrieve"],
+    r = _run(["bench.py", "--gpus", "4", "--full", "--legs", "retrieve"],
              env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0
     assert "WORLD_SIZE=2 but --gpus 4" in r.stderr
     r = _run(["bench.py", "--gpus", "0"])
     assert r.returncode != 0 and "--gpus must be >= 1" in r.stderr
+
+
+def test_bench_legs_need_full():
+    """The side legs run only behind --full: --legs without it is refused before any GPU
+    call, never silently ignored."""
+    r = _run(["bench.py", "--gpus", "1", "--legs", "retrieve"])
+    assert r.returncode == 2
+    assert "add --full" in r.stderr
+
+
+def test_bench_dump_keeps_float32_under_the_size_cap(tmp_path, monkeypatch):
+    """dump_outputs writes float32 .npy files; an array over its share of the 64 MB keeps
+    the same seeded sample of its elements on every call."""
+    sys.path.insert(0, str(ROOT))
+    import importlib
+
+    import numpy as np
+
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 4 * 100)  # 100 elements per array
+    small = np.arange(60, dtype=np.int32).reshape(6, 10)
+    large = np.arange(1000, dtype=np.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, 0, 1, {"small": small, "large": large})
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.load(tmp_path / "a" / "large.npy")
+    assert big.dtype == np.float32 and big.shape == (100,)
+    assert np.all(np.diff(big) > 0) and set(big.tolist()) <= set(large.tolist())
+    assert np.array_equal(big, np.load(tmp_path / "b" / "large.npy"))
+    bench.dump_outputs(tmp_path / "c", 1, 2, {"small": small})
+    assert [p.name for p in (tmp_path / "c").iterdir()] == ["small_rank1.npy"]
 
 
 def test_bench_self_launch_builds_the_torchrun_command(monkeypatch):

@@ -187,8 +187,8 @@ def test_bench_two_ranks_completes(tmp_path):
     env = dict(os.environ, PYTHONPATH=str(ROOT), OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", "bench.py", "--gpus", "2",
-           "--legs", "retrieve,text,rank_e2e", "--steps", "1", "--warmup", "1", "--text-docs",
-           "20000", "--queries", "512", "--no-cpu"]
+           "--full", "--legs", "retrieve,text,rank_e2e", "--steps", "1", "--warmup", "1",
+           "--text-docs", "20000", "--queries", "512", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -207,8 +207,9 @@ def test_bench_gpus_flag_launches_ranks_itself():
     1-GPU box they share the GPU over gloo (an 8-GPU node takes RCCL)."""
     env = dict(os.environ, PYTHONPATH=str(ROOT), OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--legs", "retrieve,text", "--steps", "1",
-           "--warmup", "1", "--text-docs", "20000", "--queries", "512", "--no-cpu"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--full", "--legs", "retrieve,text",
+           "--steps", "1", "--warmup", "1", "--text-docs", "20000", "--queries", "512",
+           "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -232,7 +233,7 @@ def test_bench_single_rank_rccl_path():
     env = dict(os.environ, PYTHONPATH=str(ROOT), OMP_NUM_THREADS="4", DI_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", "bench.py", "--gpus", "1",
-           "--legs", "retrieve,retrieve_shard", "--steps", "2", "--warmup", "1",
+           "--full", "--legs", "retrieve,retrieve_shard", "--steps", "2", "--warmup", "1",
            "--queries", "512", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -267,7 +268,8 @@ def test_bench_single_rank_rccl_pruned_exchange():
                DI_EXCHANGE="pruned")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", "bench.py", "--gpus", "1",
-           "--legs", "retrieve,retrieve_shard", "--steps", "3", "--warmup", "1", "--no-cpu"]
+           "--full", "--legs", "retrieve,retrieve_shard", "--steps", "3", "--warmup", "1",
+           "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]

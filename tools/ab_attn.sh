@@ -12,7 +12,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for va in ${VARIANTS:-0 4}; do
     v=${va%%:*}; a=0; [ "$va" != "$v" ] && a=${va#*:}
     DI_ATTN_X3=$v DI_ATTN_X3_ABLATE=$a timeout -k 10 ${RUN_TIMEOUT:-240} python3 "$R/bench.py" --steps 3 --warmup 1 \
-      --no-cpu --legs encode_x3 > "$OUT/v${v}a${a}_r${rep}.json" 2> "$OUT/v${v}a${a}_r${rep}.err" || exit $?
+      --no-cpu --full --legs encode_x3 > "$OUT/v${v}a${a}_r${rep}.json" 2> "$OUT/v${v}a${a}_r${rep}.err" || exit $?
     python3 - "$OUT/v${v}a${a}_r${rep}.json" "$va" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -11,7 +11,7 @@ for v in ${VALUES:?}; do
   i=$((i+1))
   out="$R/gpurun_out/$tag/run_$i"
   env "${VAR:?}=$v" timeout -k 10 ${RUN_TIMEOUT:-300} python3 "$R/bench.py" --steps ${STEPS:-3} \
-    --warmup 1 --no-cpu --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
+    --warmup 1 --no-cpu --full --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
   python3 - "$out.json" "$VAR=$v" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

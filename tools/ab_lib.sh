@@ -13,10 +13,10 @@ for v in ${VARIANTS:-old new old new}; do
   if [ "$v" = old ] || [ "$v" = mid ]; then  # baseline builds tools/_old, tools/_mid
     env DEEPIMPACT_HIP_LIB="$R/tools/_$v/libdeepimpact_hip.so" DI_LIB_ALLOW_MISSING=1 \
       timeout -k 10 ${RUN_TIMEOUT:-300} python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu \
-      --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
+      --full --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
   else
     timeout -k 10 ${RUN_TIMEOUT:-300} python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu \
-      --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
+      --full --legs "${LEGS:-encode_x3}" > "$out.json" 2> "$out.err" || exit $?
   fi
   python3 - "$out.json" "$v" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ set -o pipefail
 tag=$1; legs=${2:-retrieve,retrieve_shard}
 run() {  # name, env...
     local name=$1; shift
-    env "$@" timeout -k 10 240 python -u bench.py --legs "$legs" --steps 10 --warmup 2 --no-cpu \
+    env "$@" timeout -k 10 240 python -u bench.py --full --legs "$legs" --steps 10 --warmup 2 --no-cpu \
         > gpurun_out/${tag}_${name}.json 2> gpurun_out/${tag}_${name}.err || return 1
     python3 - "$name" gpurun_out/${tag}_${name}.json <<'PY'
 import json, sys

@@ -31,7 +31,7 @@ for s in $STEPS; do
          --timeout 300 --timeout-method thread > "$O/pytest_gpu.log" 2>&1)
       rc=$?; tail -15 "$O/pytest_gpu.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      (cd "$R" && timeout -k 10 ${BENCH_TIMEOUT:-600} python3 -u bench.py ${BENCH_ARGS:-} \
+      (cd "$R" && timeout -k 10 ${BENCH_TIMEOUT:-600} python3 -u bench.py --full ${BENCH_ARGS:-} \
          > "$O/bench.json" 2> "$O/bench.err")
       rc=$?; tail -5 "$O/bench.err"; cat "$O/bench.json"; [ $rc -eq 0 ] || exit $rc ;;
     ab)
@@ -83,7 +83,7 @@ PY
       for leg in ${STAT_LEGS:-encode_x3 retrieve retrieve_shard}; do
         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 ${STAT_TIMEOUT:-400} rocprofv3 --kernel-trace --stats \
            -d "$O/stats_$leg" -o run --output-format csv -- \
-           python3 "$R/bench.py" --legs "$leg" --steps ${STAT_STEPS:-5} --warmup 1 --no-cpu \
+           python3 "$R/bench.py" --full --legs "$leg" --steps ${STAT_STEPS:-5} --warmup 1 --no-cpu \
            > "$O/stats_$leg.json" 2> "$O/stats_$leg.err")
         rc=$?; [ $rc -eq 0 ] || { tail -20 "$O/stats_$leg.err"; exit $rc; }
         echo "stats $leg done"

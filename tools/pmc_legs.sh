@@ -17,7 +17,7 @@ for leg in ${LEGS:-retrieve_shard}; do
   for grp in "${PMC_GRPS[@]}"; do
     i=$((i+1))
     timeout -k 10 ${PASS_TIMEOUT:-300} rocprofv3 -M --pmc $grp --kernel-trace -d "$OUT/p$i" -o run \
-       --output-format csv -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu --legs "$leg" \
+       --output-format csv -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu --full --legs "$leg" \
        > "$OUT/p$i.json" 2> "$OUT/p$i.err"
     rc=$?
     if [ $rc -ne 0 ]; then tail -20 "$OUT/p$i.err"; exit $rc; fi
