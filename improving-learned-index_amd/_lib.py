@@ -44,6 +44,28 @@ class di_synth_skew(ctypes.Structure):
                 ("doc_sigma", ctypes.c_double), ("mass_max", ctypes.c_double)]
 
 
+DI_MAX_PAIR_SPECIALS = 4
+
+
+class di_pair_format(ctypes.Structure):
+    _fields_ = [("prefix", ctypes.c_int32 * DI_MAX_PAIR_SPECIALS), ("n_prefix", ctypes.c_int32),
+                ("suffix", ctypes.c_int32 * DI_MAX_PAIR_SPECIALS), ("n_suffix", ctypes.c_int32),
+                ("max_length", ctypes.c_int32)]
+
+
+def pair_format(prefix, suffix, max_length) -> di_pair_format:
+    """di_pair_format of a single-sequence template (prefix / suffix special ids)."""
+    if len(prefix) > DI_MAX_PAIR_SPECIALS or len(suffix) > DI_MAX_PAIR_SPECIALS:
+        raise ValueError(f"at most {DI_MAX_PAIR_SPECIALS} prefix and suffix ids")
+    f = di_pair_format()
+    for i, t in enumerate(prefix):
+        f.prefix[i] = int(t)
+    for i, t in enumerate(suffix):
+        f.suffix[i] = int(t)
+    f.n_prefix, f.n_suffix, f.max_length = len(prefix), len(suffix), int(max_length)
+    return f
+
+
 P = ctypes.c_void_p
 I32, I64, U32, U64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64
 
@@ -78,6 +100,10 @@ SIGNATURES = {
     "di_encoder_sync": (ctypes.c_int, [P]),
     "di_encoder_timing": (ctypes.c_int, [P, ctypes.c_char_p, P, ctypes.c_int]),
     "di_encoder_destroy": (ctypes.c_int, [P]),
+    "di_pairs_pack": (ctypes.c_int, [P, P, I32, P, P, I32, P, P, I32, P, P, I64, P, P, P,
+                                     ctypes.c_int, P, U32]),
+    "di_encode_pairs": (ctypes.c_int, [P, P, P, I32, P, P, I32, P, P, I32, P, P, U32]),
+    "di_segment_order": (ctypes.c_int, [P, P, I32, P, ctypes.c_int, P, U32]),
     "di_quantize": (ctypes.c_int, [P, I64, ctypes.c_double, I32, P, P, ctypes.c_int, P, U32]),
     "di_quantize_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, I32,
                                         ctypes.c_int, P]),
@@ -336,6 +362,62 @@ def topk_merge_device(keys, counts, n_q, n_lists, k, out_key, out_n, device=0, s
                       flags=DI_F_DEVICE_PTRS):
     check(lib().di_topk_merge(ptr(keys), ptr(counts), n_q, n_lists, k, ptr(out_key),
                               ptr(out_n), device, ctypes.c_void_p(stream), flags))
+
+
+def _is_device(a) -> bool:
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def pairs_pack(doc_tok, doc_off, qry_tok, qry_off, pair_doc, pair_qry, fmt, device=0,
+               stream=0):
+    """di_pairs_pack.  Host numpy arrays in -> (tok_ids, cu_seqlens) numpy out; torch
+    device tensors in (all of them) -> torch device tensors out.  Also returns
+    (n_tokens, max_len)."""
+    n_docs, n_q, n_pairs = len(doc_off) - 1, len(qry_off) - 1, len(pair_doc)
+    cap = max(1, n_pairs * fmt.max_length)
+    nt, ml = I64(0), I32(0)
+    if _is_device(pair_doc):
+        import torch
+
+        ids = torch.empty(cap, dtype=torch.int32, device=pair_doc.device)
+        cu = torch.empty(n_pairs + 1, dtype=torch.int32, device=pair_doc.device)
+        flags = DI_F_DEVICE_PTRS
+    else:
+        doc_tok = np.ascontiguousarray(doc_tok, np.int32)
+        qry_tok = np.ascontiguousarray(qry_tok, np.int32)
+        doc_off = np.ascontiguousarray(doc_off, np.int64)
+        qry_off = np.ascontiguousarray(qry_off, np.int64)
+        pair_doc = np.ascontiguousarray(pair_doc, np.int32)
+        pair_qry = np.ascontiguousarray(pair_qry, np.int32)
+        ids = np.zeros(cap, np.int32)
+        cu = np.zeros(n_pairs + 1, np.int32)
+        flags = 0
+    check(lib().di_pairs_pack(ptr(doc_tok), ptr(doc_off), n_docs, ptr(qry_tok), ptr(qry_off),
+                              n_q, ptr(pair_doc), ptr(pair_qry), n_pairs, ctypes.byref(fmt),
+                              ptr(ids), cap, ptr(cu), ctypes.byref(nt), ctypes.byref(ml),
+                              device, ctypes.c_void_p(stream or 0), flags))
+    return ids[:nt.value], cu, nt.value, ml.value
+
+
+def segment_order(scores, cu_seg, device=0, stream=0):
+    """di_segment_order: per segment the positions in the order of Python's
+    sorted(..., key=score, reverse=True).  numpy in -> numpy out, torch device tensors in
+    -> a torch device tensor out."""
+    n_seg = len(cu_seg) - 1
+    if _is_device(scores):
+        import torch
+
+        out = torch.empty(max(1, scores.numel()), dtype=torch.int32, device=scores.device)
+        check(lib().di_segment_order(ptr(scores), ptr(cu_seg), n_seg, ptr(out), device,
+                                     ctypes.c_void_p(stream or 0), DI_F_DEVICE_PTRS))
+        return out[:scores.numel()]
+    scores = np.ascontiguousarray(scores, np.float32)
+    cu_seg = np.ascontiguousarray(cu_seg, np.int32)
+    out = np.zeros(max(1, scores.size), np.int32)
+    check(lib().di_segment_order(ptr(scores if scores.size else np.zeros(1, np.float32)),
+                                 ptr(cu_seg), n_seg, ptr(out), device,
+                                 ctypes.c_void_p(stream or 0), 0))
+    return out[:scores.size]
 
 
 def key_doc(keys, wide=False):

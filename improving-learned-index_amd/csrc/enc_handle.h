@@ -1,0 +1,51 @@
+// enc_handle.h -- the encoder handle (weights + workspace of one device), shared by the
+// files that run a forward on it: encoder.hip (di_encode) and cross.hip (di_encode_pairs).
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "di_common.h"
+
+namespace di {
+
+struct Layer {
+    DevBuf w_qkv, b_qkv, w_o, b_o, ln1_g, ln1_b, w_i, b_i, w_out, b_out, ln2_g, ln2_b;
+    DevBuf s_qkv, c_qkv, s_i, c_i;  // LN folding: per-column s = W' 1, c = b + W beta
+};
+
+}  // namespace di
+
+struct di_encoder {
+    di_encoder_cfg cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    size_t esz = 2;  // bytes per activation/weight element (bf16 or f32)
+    // fp32-faithful split-bf16 mode (DI_PREC_BF16X3): esz = 4 sizes the workspace (a
+    // split row of 2H bf16 = an f32 row), f32 tables, GEMM weights [N][3K] bf16
+    bool split = false;
+    di::DevBuf word, pos, type0, emb_g, emb_b, head_w;
+    float head_b = 0.f;
+    std::vector<std::unique_ptr<di::Layer>> layers;
+    // workspace
+    di::DevBuf X, qk, vt, vcol, ctx, pre, X1, Hff, impact, ids, cu, tt, cut, err;
+    // LayerNorm folding (bf16): the GEMM consuming LN(x) reads x and folds LN in
+    bool folded = false;
+    di::DevBuf stats1, stats2, head_wg;  // row-statistics partials; w * gamma_last
+    di::DevBuf rln1, rln2;               // per-row (rstd, -rstd mean) of P1 / P2
+    float head_sw = 0.f, head_cw = 0.f;
+    int64_t cap_tokens = 0;
+    int64_t cap_rows = 0;  // allocated rows of the GEMM A operands (>= cap_tokens)
+    int cap_docs = 0;
+    int ld_v = 0;
+    di::DevBuf pinfo;  // di_encode_pairs: (n_tokens, max_len, error bits) of the pack
+    di::Timer timer;
+};
+
+namespace di {
+
+// Grows the workspace to M tokens / n_docs documents / n_terms kept rows (never shrinks).
+void ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms);
+
+}  // namespace di

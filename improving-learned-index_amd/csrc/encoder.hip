@@ -21,6 +21,7 @@
 
 #include "di_common.h"
 #include "enc_common.h"
+#include "enc_handle.h"
 
 namespace di {
 
@@ -70,40 +71,9 @@ void launch_gather_terms(const float *impact, const int32_t *cu_seq, const int32
                          int n_docs, const int32_t *term_tok, int n_terms, int do_round,
                          float *out, int32_t *err, hipStream_t s);
 
-struct Layer {
-    DevBuf w_qkv, b_qkv, w_o, b_o, ln1_g, ln1_b, w_i, b_i, w_out, b_out, ln2_g, ln2_b;
-    DevBuf s_qkv, c_qkv, s_i, c_i;  // LN folding: per-column s = W' 1, c = b + W beta
-};
-
 }  // namespace di
 
 using namespace di;
-
-struct di_encoder {
-    di_encoder_cfg cfg{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    size_t esz = 2;  // bytes per activation/weight element (bf16 or f32)
-    // fp32-faithful split-bf16 mode (DI_PREC_BF16X3): esz = 4 sizes the workspace (a
-    // split row of 2H bf16 = an f32 row), f32 tables, GEMM weights [N][3K] bf16
-    bool split = false;
-    DevBuf word, pos, type0, emb_g, emb_b, head_w;
-    float head_b = 0.f;
-    std::vector<std::unique_ptr<Layer>> layers;
-    // workspace
-    DevBuf X, qk, vt, vcol, ctx, pre, X1, Hff, impact, ids, cu, tt, cut, err;
-    // LayerNorm folding (bf16): the GEMM consuming LN(x) reads x and folds LN in
-    bool folded = false;
-    DevBuf stats1, stats2, head_wg;  // row-statistics partials; w * gamma_last
-    DevBuf rln1, rln2;               // per-row (rstd, -rstd mean) of P1 / P2
-    float head_sw = 0.f, head_cw = 0.f;
-    int64_t cap_tokens = 0;
-    int64_t cap_rows = 0;  // allocated rows of the GEMM A operands (>= cap_tokens)
-    int cap_docs = 0;
-    int ld_v = 0;
-    Timer timer;
-};
 
 namespace {
 
@@ -259,7 +229,9 @@ void upload_split3(DevBuf &dst, const std::vector<const HostTensor *> &parts, in
     DI_HIP(hipMemcpy(dst.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
 }
 
-void ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms) {
+}  // namespace
+
+void di::ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms) {
     const int H = e->cfg.hidden, F = e->cfg.intermediate;
     if (M > e->cap_tokens || n_docs > e->cap_docs) {
         int64_t cap = std::max<int64_t>(std::max<int64_t>(M, e->cap_tokens), 256);
@@ -302,6 +274,8 @@ void ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms) {
     e->tt.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
     e->err.reserve(16);
 }
+
+namespace {
 
 template <typename T>
 void forward(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_docs, int64_t M,

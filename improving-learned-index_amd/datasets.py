@@ -3,10 +3,12 @@ src/utils/datasets.py pieces on the hot path (Appendix A of SURVEY.md)."""
 from __future__ import annotations
 
 import json
+import logging
 from pathlib import Path
 from typing import Dict, Iterable, Iterator, Optional, Set, Tuple, Union
 
 COLLECTION_TYPES = ["msmarco", "beir"]
+logger = logging.getLogger(__name__)
 
 
 class CollectionParser:
@@ -120,6 +122,47 @@ class Collection:
 
     def __iter__(self):
         return iter(self.collection.items())
+
+
+class TopKDataset:
+    """datasets.py:181-222: lines qid \\t pid \\t query \\t passage -> queries, passages
+    and, per qid, its candidate pids in file order."""
+
+    def __init__(self, top_k_path: Union[str, Path]):
+        self.queries, self.passages, self.top_k = self._load_topK(top_k_path)
+
+    def _load_topK(self, path):
+        queries: Dict[str, str] = {}
+        passages: Dict[str, str] = {}
+        top_k: Dict[str, list] = {}
+        with open(path, "r", encoding="utf-8") as f:
+            for line in f:
+                qid, pid, query, passage = line.strip().split("\t")
+                qid, pid = str(qid), str(pid)
+                assert (qid not in queries) or (queries[qid] == query), \
+                    "TopK file is not in the expected format"
+                queries[qid] = query
+                passages[pid] = passage
+                top_k.setdefault(qid, []).append(pid)
+        assert all(len(top_k[qid]) == len(set(top_k[qid])) for qid in top_k), \
+            "TopK file contains duplicates"
+        lens = [len(top_k[qid]) for qid in top_k]
+        self.min_len = min(lens)
+        self.max_len = max(lens)
+        self.avg_len = round(sum(lens) / len(top_k), 2)
+        logger.info(f"Loaded {len(top_k)} queries.")
+        logger.info(f"Top K Passages distribution: min={self.min_len}, max={self.max_len}, "
+                    f"avg={self.avg_len}")
+        return queries, passages, top_k
+
+    def __len__(self):
+        return len(self.top_k)
+
+    def __getitem__(self, qid):
+        return self.top_k[str(qid)]
+
+    def keys(self):
+        return self.top_k.keys()
 
 
 class RunFile:

@@ -191,6 +191,33 @@ class DeviceEncoder:
         check(lib().di_encode(self._h, ptr(ids), ptr(cu_seqlens), n_docs, n_tokens, max_len,
                               ptr(term_tok), ptr(cu_terms), n_terms, ptr(out), flags))
 
+    def encode_pairs(self, doc_tok, doc_off, qry_tok, qry_off, pair_doc, pair_qry, fmt,
+                     out=None, timing=False):
+        """di_encode_pairs: the cross-encoder score of every (passage, query part) pair,
+        sequences assembled on the device (cross_encoder.py:9-23).  Host numpy arrays in
+        -> numpy float32 [n_pairs]; torch device tensors in (all of them, on this
+        encoder's device; `out` optional) -> a torch device tensor."""
+        n_docs, n_q, n_pairs = len(doc_off) - 1, len(qry_off) - 1, len(pair_doc)
+        flags = _lib.DI_F_TIMING if timing else 0
+        if _lib._is_device(pair_doc):
+            import torch
+
+            if out is None:
+                out = torch.empty(max(1, n_pairs), dtype=torch.float32, device=pair_doc.device)
+            flags |= _lib.DI_F_DEVICE_PTRS
+        else:
+            doc_tok = np.ascontiguousarray(doc_tok, np.int32)
+            qry_tok = np.ascontiguousarray(qry_tok, np.int32)
+            doc_off = np.ascontiguousarray(doc_off, np.int64)
+            qry_off = np.ascontiguousarray(qry_off, np.int64)
+            pair_doc = np.ascontiguousarray(pair_doc, np.int32)
+            pair_qry = np.ascontiguousarray(pair_qry, np.int32)
+            out = np.zeros(max(1, n_pairs), np.float32)
+        check(lib().di_encode_pairs(self._h, ptr(doc_tok), ptr(doc_off), n_docs, ptr(qry_tok),
+                                    ptr(qry_off), n_q, ptr(pair_doc), ptr(pair_qry), n_pairs,
+                                    ctypes.byref(fmt), ptr(out), flags))
+        return out[:n_pairs]
+
     def reserve(self, max_tokens, max_docs, max_terms):
         check(lib().di_encoder_reserve(self._h, max_tokens, max_docs, max_terms))
 

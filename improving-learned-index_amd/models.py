@@ -418,6 +418,152 @@ class DeepImpact:
         return self.encode_documents(documents, round3=False)
 
 
+# --------------------------------------------------------------------------- cross-encoder
+def pack_pairs_host(doc_tok, doc_off, qry_tok, qry_off, pair_doc, pair_qry, prefix, suffix,
+                    max_length):
+    """The pack rule of di_pairs_pack in numpy: sequence p = prefix ++ the first
+    max_length - len(prefix) - len(suffix) tokens of (passage pair_doc[p] ++ query part
+    pair_qry[p]) ++ suffix -- the tokenizer's right truncation of a single sequence.
+    Returns (tok_ids int32, cu_seqlens int32 [n_pairs + 1])."""
+    doc_tok, qry_tok = np.asarray(doc_tok, np.int32), np.asarray(qry_tok, np.int32)
+    budget = max_length - len(prefix) - len(suffix)
+    if budget < 0:
+        raise ValueError("max_length is smaller than the number of special tokens")
+    pre, suf = np.asarray(prefix, np.int32), np.asarray(suffix, np.int32)
+    parts, cu = [], [0]
+    for d, q in zip(pair_doc, pair_qry):
+        if not (0 <= d < len(doc_off) - 1 and 0 <= q < len(qry_off) - 1):
+            raise IndexError("a pair index is outside its token store")
+        content = np.concatenate([doc_tok[doc_off[d]:doc_off[d + 1]],
+                                  qry_tok[qry_off[q]:qry_off[q + 1]]])[:budget]
+        parts += [pre, content, suf]
+        cu.append(cu[-1] + len(pre) + len(content) + len(suf))
+    ids = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return ids, np.asarray(cu, np.int32)
+
+
+class TokenStore:
+    """Token ids of a list of texts back to back (no special tokens): tok int32,
+    off int64 [n + 1]; on the device after to_device()."""
+
+    def __init__(self, encodings_ids: Sequence[Sequence[int]]):
+        lens = np.fromiter((len(x) for x in encodings_ids), np.int64, count=len(encodings_ids))
+        self.off = np.zeros(len(lens) + 1, np.int64)
+        self.off[1:] = np.cumsum(lens)
+        self.tok = np.fromiter((t for x in encodings_ids for t in x), np.int32,
+                               count=int(self.off[-1]))
+        self.d_tok = self.d_off = None
+
+    def __len__(self):
+        return len(self.off) - 1
+
+    def to_device(self, device: int):
+        import torch
+
+        dev = torch.device("cuda", device)
+        self.d_tok = torch.from_numpy(self.tok if self.tok.size else np.zeros(1, np.int32)).to(dev)
+        self.d_off = torch.from_numpy(self.off).to(dev)
+        return self
+
+
+class DeepImpactCrossEncoder(DeepImpact):
+    """Cross-encoder head on the same encoder (src/deep_impact/models/cross_encoder.py:9-51):
+    the impact head applied to token 0 of f'{document} [SEP] {query}'."""
+
+    SEPARATOR = " [SEP] "
+
+    @classmethod
+    def process_cross_encoder_document_and_query(cls, document: str, query: str,
+                                                 max_length: Optional[int] = None):
+        """cross_encoder.py:25-37: the joined string's encoding, unpadded, truncated to
+        max_length."""
+        return cls._tok(max_length or cls.max_length).encode(f"{document} [SEP] {query}")
+
+    @classmethod
+    def process_cross_encoder_documents_and_query(cls, documents: Sequence[str], query: str,
+                                                  max_length: Optional[int] = None):
+        """cross_encoder.py:39-51."""
+        return cls._tok(max_length or cls.max_length).encode_batch(
+            [f"{document} [SEP] {query}" for document in documents])
+
+    # ---- split tokenization: each passage and each query once
+    @classmethod
+    def pair_template(cls, max_length: Optional[int] = None) -> Tuple[List[int], List[int]]:
+        """(prefix ids, suffix ids) the tokenizer's post-processor puts around a single
+        sequence."""
+        tok = cls._tok(max_length or cls.max_length)
+        e = tok.encode("a")
+        body = [i for i, w in enumerate(e.word_ids) if w is not None]
+        return list(e.ids[:body[0]]), list(e.ids[body[-1] + 1:])
+
+    @classmethod
+    def tokenize_passages(cls, passages: Sequence[str], max_length: Optional[int] = None
+                          ) -> TokenStore:
+        """Passage part of a pair: ids(passage.rstrip()), no special tokens.  (A part
+        keeps at least the tokens any sequence can take from it.)"""
+        tok = cls._tok(max_length or cls.max_length)
+        return TokenStore([e.ids for e in tok.encode_batch([p.rstrip() for p in passages],
+                                                           add_special_tokens=False)])
+
+    @classmethod
+    def tokenize_queries(cls, queries: Sequence[str], max_length: Optional[int] = None
+                         ) -> TokenStore:
+        """Query part of a pair: ids('[SEP] ' + query) -- the separator is tokenized with
+        the query, whose trailing whitespace stays; no special tokens."""
+        tok = cls._tok(max_length or cls.max_length)
+        return TokenStore([e.ids for e in tok.encode_batch(["[SEP] " + q for q in queries],
+                                                           add_special_tokens=False)])
+
+    def pair_format(self, max_length: Optional[int] = None):
+        ml = max_length or self.max_length
+        pre, suf = self.pair_template(ml)
+        return _lib.pair_format(pre, suf, ml)
+
+    def score_pairs(self, doc_store: TokenStore, query_store: TokenStore, pair_doc, pair_qry,
+                    max_length: Optional[int] = None, timing: bool = False):
+        """Scores of the pairs (doc_store[pair_doc[p]], query_store[pair_qry[p]]), float32
+        [n_pairs] -- di_encode_pairs.  Stores that are on the device (to_device) are read
+        there and the result is a torch device tensor; otherwise numpy in, numpy out."""
+        fmt = self.pair_format(max_length)
+        if doc_store.d_tok is not None and query_store.d_tok is not None:
+            import torch
+
+            dev = doc_store.d_tok.device
+            pd = torch.as_tensor(np.ascontiguousarray(pair_doc, np.int32)).to(dev) \
+                if not hasattr(pair_doc, "data_ptr") else pair_doc
+            pq = torch.as_tensor(np.ascontiguousarray(pair_qry, np.int32)).to(dev) \
+                if not hasattr(pair_qry, "data_ptr") else pair_qry
+            return self.encoder.encode_pairs(doc_store.d_tok, doc_store.d_off, query_store.d_tok,
+                                             query_store.d_off, pd, pq, fmt, timing=timing)
+        return self.encoder.encode_pairs(doc_store.tok, doc_store.off, query_store.tok,
+                                         query_store.off, pair_doc, pair_qry, fmt, timing=timing)
+
+    def score_packed(self, ids, cu_seqlens):
+        """Token-0 impact of every packed sequence through the per-token forward -- the
+        literal reference route (last_hidden_state[:, 0, :], cross_encoder.py:22-23)."""
+        cu = np.asarray(cu_seqlens, np.int64)
+        if len(cu) <= 1:
+            return np.zeros(0, np.float32)
+        tok = self.encoder.encode_packed(ids, cu_seqlens, token_impacts=True)
+        return tok[cu[:-1]]
+
+    def __call__(self, input_ids, attention_mask, token_type_ids=None):
+        """Reference forward protocol (cross_encoder.py:9-23): padded [B, S] batch in,
+        scores [B, 1] (float32, host) out.  token_type_ids are accepted and unused, as in
+        the reference (original.py:79-84)."""
+        import torch
+
+        ids = np.asarray(input_ids.cpu() if hasattr(input_ids, "cpu") else input_ids)
+        mask = np.asarray(attention_mask.cpu() if hasattr(attention_mask, "cpu")
+                          else attention_mask).astype(bool)
+        cu = np.zeros(len(ids) + 1, np.int32)
+        cu[1:] = np.cumsum(mask.sum(1))
+        n = len(ids)
+        out = self.encoder.encode_packed(ids[mask].astype(np.int32), cu,
+                                         np.zeros(n, np.int32), np.arange(n + 1, dtype=np.int32))
+        return torch.from_numpy(np.array(out, np.float32)).unsqueeze(-1)
+
+
 # --------------------------------------------------------------------------- weights
 def _load_weights(checkpoint_path, config, variant):
     import torch

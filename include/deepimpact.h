@@ -283,6 +283,69 @@ int di_encoder_timing(di_encoder *enc, const char *name, di_timing *out, int res
 int di_encoder_destroy(di_encoder *enc);
 
 /* ======================================================================
+ * Cross-encoder reranking: pairs packed on the device, scored, ranked
+ * ====================================================================== */
+#define DI_MAX_PAIR_SPECIALS 4 /* special tokens in front of / behind a pair's content */
+
+/* The single-sequence template of the tokenizer's post-processor ("<s> $A </s>",
+ * "[CLS] $A [SEP]") and the truncation length of enable_truncation(max_length). */
+typedef struct di_pair_format {
+    int32_t prefix[DI_MAX_PAIR_SPECIALS];
+    int32_t n_prefix;
+    int32_t suffix[DI_MAX_PAIR_SPECIALS];
+    int32_t n_suffix;
+    int32_t max_length;
+} di_pair_format;
+
+/* Replaces process_cross_encoder_documents_and_query's encode_batch of
+ * f'{document} [SEP] {query}' (src/deep_impact/models/cross_encoder.py:39-51) for a
+ * batch of pairs whose two parts were tokenized once each (no special tokens):
+ * doc_tok / qry_tok are token stores, CSR by doc_off[n_docs+1] / qry_off[n_q+1];
+ * pair p joins passage pair_doc[p] and query part pair_qry[p].  Sequence p =
+ * prefix ++ the first max_length - n_prefix - n_suffix tokens of (doc ++ qry) ++
+ * suffix -- the tokenizer's right truncation of a single sequence; the cut may fall
+ * inside the passage (no query token survives) or inside the query part.
+ * Writes tok_ids (capacity tok_cap tokens; n_pairs * max_length always suffices) and
+ * cu_seqlens[n_pairs+1] in di_encode's layout, and *n_tokens / *max_len on the host.
+ * Host pointers, or device pointers with DI_F_DEVICE_PTRS (fmt, n_tokens and max_len
+ * are always host).  Runs on hip_stream and waits for it once, to read the sizes back;
+ * with DI_F_DEVICE_PTRS | DI_F_ASYNC the copy into tok_ids is still in flight at
+ * return.  A pair index outside its store: DI_EINVAL (an error bit set on the device,
+ * as di_encode reports a bad term index); *n_tokens > tok_cap: DI_ERANGE with
+ * *n_tokens set. */
+int di_pairs_pack(const int32_t *doc_tok, const int64_t *doc_off, int32_t n_docs,
+                  const int32_t *qry_tok, const int64_t *qry_off, int32_t n_q,
+                  const int32_t *pair_doc, const int32_t *pair_qry, int32_t n_pairs,
+                  const di_pair_format *fmt, int32_t *tok_ids, int64_t tok_cap,
+                  int32_t *cu_seqlens, int64_t *n_tokens, int32_t *max_len, int device,
+                  void *hip_stream, uint32_t flags);
+
+/* Replaces DeepImpactCrossEncoder.forward (src/deep_impact/models/cross_encoder.py:9-23:
+ * the impact head on last_hidden_state[:, 0, :]) over the sequences of di_pairs_pack,
+ * i.e. one batch step of CrossEncoderReRanker.rerank
+ * (src/deep_impact/evaluation/cross_encoder_reranker.py:41-60): packs into the
+ * encoder's workspace and runs di_encode's forward with token 0 of every sequence as
+ * its only kept row, so the bf16 / bf16x3 pruned last layer computes n_pairs rows.
+ * out_scores[n_pairs].  Token-type ids are no input: the reference's forward never
+ * passes them on (src/deep_impact/models/original.py:79-84).  max_length <=
+ * max_positions.  Flags: DI_F_DEVICE_PTRS, DI_F_ASYNC (the size read-back still waits
+ * once), DI_F_TIMING ("pairs_scan", "pairs_copy" beside di_encode's kernels). */
+int di_encode_pairs(di_encoder *enc, const int32_t *doc_tok, const int64_t *doc_off,
+                    int32_t n_docs, const int32_t *qry_tok, const int64_t *qry_off, int32_t n_q,
+                    const int32_t *pair_doc, const int32_t *pair_qry, int32_t n_pairs,
+                    const di_pair_format *fmt, float *out_scores, uint32_t flags);
+
+/* Replaces sorted(zip(top_k_pids, scores), key=lambda x: x[1], reverse=True)
+ * (src/deep_impact/evaluation/cross_encoder_reranker.py:62) for n_seg queries at once:
+ * scores CSR by cu_seg[n_seg+1]; out_pos[cu_seg[s] + r] = the position (within segment
+ * s) of its rank-r candidate -- score descending, equal scores in input order (-0.0
+ * equals +0.0).  NaN scores are outside the contract.  Segments of up to DI_MAX_TOPK
+ * scores; a longer one fails the call with DI_ERANGE (with DI_F_DEVICE_PTRS its out_pos
+ * entries are -1).  Waits for hip_stream before returning. */
+int di_segment_order(const float *scores, const int32_t *cu_seg, int32_t n_seg, int32_t *out_pos,
+                     int device, void *hip_stream, uint32_t flags);
+
+/* ======================================================================
  * 8-bit quantizer                                          (A10)
  * ====================================================================== */
 /* Replaces quantize_file's arithmetic (src/deep_impact/indexing/quantize.py:13-47):
