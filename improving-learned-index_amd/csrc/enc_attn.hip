@@ -665,7 +665,10 @@ static_assert((KC == 64 && IMG == 16384) || (KC == 32 && IMG == 8192), "AX_SEL's
                     const auto p32 = __builtin_amdgcn_permlane32_swap(
                         __float_as_uint(cmax), __float_as_uint(cmax), false, false);
                     cmax = fmaxf(__uint_as_float(p32[0]), __uint_as_float(p32[1]));
-                    const float m_new = fmaxf(m[qt], cmax);
+                    // (per query: a row whose own scores stay under its limit keeps its
+                    // reference, whatever the tile's other rows do -- its arithmetic must
+                    // not depend on which queries share the tile, see the pruned last layer)
+                    const float m_new = cmax > lim[qt] ? fmaxf(m[qt], cmax) : m[qt];
                     if (m_new != m[qt]) {
                         const float alpha = __builtin_amdgcn_exp2f((m[qt] - m_new) * sc);
                         lsum[qt] *= alpha;
@@ -803,7 +806,8 @@ static_assert((KC == 64 && IMG == 16384) || (KC == 32 && IMG == 8192), "AX_SEL's
                         const auto p32 = __builtin_amdgcn_permlane32_swap(
                             __float_as_uint(cmax), __float_as_uint(cmax), false, false);
                         cmax = fmaxf(__uint_as_float(p32[0]), __uint_as_float(p32[1]));
-                        const float m_new = fmaxf(m[qt], cmax);
+                        // (per query, as the PIPE form)
+                        const float m_new = cmax > lim[qt] ? fmaxf(m[qt], cmax) : m[qt];
                         if (m_new != m[qt]) {  // (per lane; 0 at the first)
                             const float alpha = __builtin_amdgcn_exp2f((m[qt] - m_new) * sc);
                             lsum[qt] *= alpha;
@@ -1015,8 +1019,8 @@ __device__ __forceinline__ bool softmax_need(const f32x4 (&s)[2], float lim) {
         for (int r = 0; r < 4; ++r) need |= s[t][r] > lim;
     return need;
 }
-__device__ __forceinline__ void softmax_rescale(const f32x4 (&s)[2], float &m, float &msc,
-                                                f32x4 (&o)[4], f32x4 &l) {
+__device__ __forceinline__ void softmax_rescale(const f32x4 (&s)[2], float lim, float &m,
+                                                float &msc, f32x4 (&o)[4], f32x4 &l) {
     constexpr float sc = 0.125f * 1.4426950408889634f;
     float cmax = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])),
                        fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
@@ -1026,7 +1030,10 @@ __device__ __forceinline__ void softmax_rescale(const f32x4 (&s)[2], float &m, f
     const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(cmax),
                                                       __float_as_uint(cmax), false, false);
     cmax = fmaxf(__uint_as_float(p32[0]), __uint_as_float(p32[1]));
-    const float m_new = fmaxf(m, cmax);
+    // per query: only a row with a score of its own above its limit moves its reference
+    // (alpha = 1 exactly for the others), so that a row's arithmetic does not depend on
+    // which queries share its tile -- the pruned last layer regroups them
+    const float m_new = cmax > lim ? fmaxf(m, cmax) : m;
     const float alpha = exp2f((m - m_new) * sc);  // 0 on the first chunk
     m = m_new;
     msc = m_new * sc;
@@ -1111,9 +1118,12 @@ attention_v3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
     const uint32_t lds_base =
         (uint32_t)(uintptr_t)((__attribute__((address_space(3))) unsigned char *)lds);
 
-    // pair -> (doc, head): p / n_heads by a multiply-high (exact for p < 2^32 / n_heads)
+    // pair -> (doc, head): p / n_heads by a multiply-high (exact for p < 2^32 / n_heads);
+    // one head: the magic number would be 2^32, the pair is the document
     const uint32_t heads_magic = 0xFFFFFFFFu / (uint32_t)n_heads + 1u;
-    auto doc_of = [&](int pp) { return (int)__umulhi((uint32_t)pp, heads_magic); };
+    auto doc_of = [&](int pp) {
+        return n_heads == 1 ? pp : (int)__umulhi((uint32_t)pp, heads_magic);
+    };
 
     // LDS-DMA of pair p's K and V rows < round32(n) into buffer b, through a buffer
     // resource spanning the document's rows only: rows past n read zeros (their scores
@@ -1389,7 +1399,7 @@ attention_v3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
 #pragma unroll
                     for (int qt = 0; qt < NQ; ++qt)
                         if (__any(need[qt])) {
-                            softmax_rescale(s[qt], m[qt], msc[qt], o[qt], l[qt]);
+                            softmax_rescale(s[qt], lim[qt], m[qt], msc[qt], o[qt], l[qt]);
                             lim[qt] = m[qt] + 8.0f / (0.125f * 1.4426950408889634f);
                         }
                 }

@@ -244,7 +244,8 @@ void di::ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms)
         e->X1.reserve(capr * H * es);
         e->ctx.reserve(capr * H * es);
         e->qk.reserve(cap * 3 * H * es);  // [M][3H] (v3 path) or [M][2H] + V^T
-        e->Hff.reserve(capr * F * es);
+        // (Hff also holds the pruned last layer's gathered rows, H wide: F < H is accepted)
+        e->Hff.reserve(capr * std::max(F, H) * es);
         e->pre.reserve(cap * H * es);
         e->impact.reserve(cap * 4);
         e->ids.reserve(cap * 4);
