@@ -7,8 +7,9 @@
 //
 // Float32 accumulation (numpy >= 2 semantics of `0.0 + np.float32`, the
 // environment the reference runs in here): terms are applied one
-// after the other with a barrier in between and each doc occurs once per term, so
-// every doc's sum is formed in exactly the reference's order -- bit-exact scores.
+// after the other with a barrier in between and each doc occurs once per term
+// (di_sparse_create rejects a term that names a doc twice), so every doc's sum is
+// formed in exactly the reference's order -- bit-exact scores.
 //
 // Layout: docs in blocks of SP_DOCS = 16384; per term, postings grouped by block
 // (doc ascending inside); SoA: u16 doc-in-block + f32 impact.
@@ -471,13 +472,20 @@ int di_sparse_create(const int64_t *term_off, int64_t n_terms, const uint32_t *p
         std::vector<int64_t> tstart(std::max<int64_t>(n_terms, 1), 0);
         std::vector<uint32_t> boff((size_t)std::max<int64_t>(n_terms * stride, 1), 0);
         std::vector<uint32_t> cnt(stride);
+        // the last term that kept a posting of each doc: the score kernels apply a term's
+        // postings with a plain read-modify-write, exact only with one posting per doc
+        std::vector<int64_t> last_term(n_docs, -1);
         int64_t total = 0;
         for (int64_t t = 0; t < n_terms; ++t) {
             DI_REQUIRE(term_off[t + 1] >= term_off[t], DI_EINVAL, "term_off not monotone");
             std::fill(cnt.begin(), cnt.end(), 0);
             for (int64_t p = term_off[t]; p < term_off[t + 1]; ++p) {
                 DI_REQUIRE(pdoc[p] < n_docs, DI_EINVAL, "doc %u >= n_docs", pdoc[p]);
-                if (pimp[p] > 0.f) cnt[pdoc[p] / SP_DOCS]++;  // nano_beir_evaluator.py:98
+                if (!(pimp[p] > 0.f)) continue;  // nano_beir_evaluator.py:98
+                DI_REQUIRE(last_term[pdoc[p]] != t, DI_EINVAL,
+                           "term %lld has two postings for doc %u", (long long)t, pdoc[p]);
+                last_term[pdoc[p]] = t;
+                cnt[pdoc[p] / SP_DOCS]++;
             }
             tstart[t] = total;
             uint32_t run = 0;

@@ -197,7 +197,10 @@ typedef struct di_sparse di_sparse;
 
 /* Replaces SparseSearch._build_inverted_index (nano_beir_evaluator.py:78-101):
  * per term, postings (doc = corpus position, float32 impact) in corpus order;
- * impacts <= 0 are dropped (:98).  n_docs <= DI_MAX_SPARSE_DOCS. */
+ * impacts <= 0 are dropped (:98).  n_docs <= DI_MAX_SPARSE_DOCS.
+ * Precondition: among the kept postings of one term every doc occurs at most once
+ * (the reference would add both impacts; the scorer applies a term's postings in
+ * parallel); a term that repeats a doc fails the call with DI_EINVAL. */
 int di_sparse_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pdoc,
                      const float *pimp, uint32_t n_docs, int device, di_sparse **out);
 

@@ -5,7 +5,8 @@ exactly the ones the exchange's definition selects (T_q = the ceil(k/g)-th large
 sample of the union, every key >= T_q), and their merge must equal the merge of the
 full lists (parallel.exchange_topk; /root/reference/src/deep_impact/evaluation/
 ranker.py:43-48 keeps the global top-k).  Lists as test_exchange_cpu builds them:
-ragged counts, rejected queries, keys past the sign bit."""
+ragged counts, rejected queries, keys past the sign bit.  The chain ends as
+parallel._exchange_merge does: di_topk_merge on the gathered device lists, lists-major."""
 import numpy as np
 import pytest
 import torch
@@ -24,7 +25,7 @@ def L():
     return _lib
 
 
-def _run_device_steps(L, keys, cnt, k, g):
+def _run_device_steps(L, keys, cnt, k, g, merged):
     lib, P = L.lib(), L.ptr
     W, nq, _ = keys.shape
     dev = torch.device("cuda", 0)
@@ -57,7 +58,14 @@ def _run_device_steps(L, keys, cnt, k, g):
     g_n = torch.empty(W * nq, dtype=torch.int32, device=dev)
     L.check(lib.di_xchg_unpack(P(g2) if emax else None, emax, P(gec), P(off), W, nq, k, P(out),
                                P(g_n), 0, st))
+    # the production chain's last step (parallel._exchange_merge): di_topk_merge over the
+    # gathered [world][nq][k] lists where they lie, lists-major on device pointers
+    mk = torch.full((nq * k,), -1, dtype=torch.int64, device=dev)
+    mn = torch.full((nq,), -7, dtype=torch.int32, device=dev)
+    L.topk_merge_device(out, g_n, nq, W, k, mk, mn, device=0, stream=st,
+                        flags=L.DI_F_DEVICE_PTRS | L.DI_F_LISTS_MAJOR)
     torch.cuda.synchronize()
+    merged.append((mk.cpu().numpy().view(np.uint64).reshape(nq, k), mn.cpu().numpy()))
     return (out.cpu().numpy().view(np.uint64).reshape(W, nq, k), g_n.cpu().numpy().reshape(W, nq),
             gs.cpu().numpy().view(np.uint64).reshape(W, nq, s_n), tot.cpu().numpy())
 
@@ -69,7 +77,8 @@ def test_device_exchange_steps_equal_definition(L, world, k, mode):
     nq = 24 if world < 64 else 4
     keys, cnt = _lists(world, nq, k, seed=3 + world + k, mode=mode)
     g = max(1, min(64, k // (4 * world)))
-    out, g_n, gs, tot = _run_device_steps(L, keys, cnt, k, g)
+    merged = []
+    out, g_n, gs, tot = _run_device_steps(L, keys, cnt, k, g, merged)
     s_n, need = k // g, -(-k // g)
     for q in range(nq):
         # the definition, in numpy: samples, T_q, this rank's keys >= T_q
@@ -93,5 +102,12 @@ def test_device_exchange_steps_equal_definition(L, world, k, mode):
     got, want = _merge(out, g_n, k), _merge(keys, cnt, k)
     for q in range(nq):
         assert got[q] == want[q], q
+    # ... and so is the device merge of the exchanged lists (a rejected query: -1)
+    (mk, mn), = merged
+    for q in range(nq):
+        if want[q] is None:
+            assert mn[q] == -1, q
+        else:
+            assert mn[q] == len(want[q]) and mk[q, :mn[q]].tolist() == want[q], q
     if world >= 2 and mode == "iid":  # doc-id-sharded lists: well under k keys per rank
         assert tot.max() / nq < 0.6 * k + s_n
