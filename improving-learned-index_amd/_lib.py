@@ -95,6 +95,8 @@ SIGNATURES = {
     "di_xchg_unpack": (ctypes.c_int, [P, I64, P, P, I32, I32, I32, P, P, ctypes.c_int, P]),
     "di_encoder_create": (ctypes.c_int, [P, P, I32, ctypes.c_int, P]),
     "di_encode": (ctypes.c_int, [P, P, P, I32, I64, I32, P, P, I64, P, U32]),
+    "di_encode_pairwise": (ctypes.c_int, [P, P, P, I32, I64, I32, P, P, I64, P, I64, P, P, P,
+                                          U32]),
     "di_encoder_reserve": (ctypes.c_int, [P, I64, I32, I64]),
     "di_encoder_set_stream": (ctypes.c_int, [P, P]),
     "di_encoder_sync": (ctypes.c_int, [P]),

@@ -14,6 +14,14 @@ struct Layer {
     DevBuf s_qkv, c_qkv, s_i, c_i;  // LN folding: per-column s = W' 1, c = b + W beta
 };
 
+// One di_encode_pairwise call in flight: what the forwards hand to pair_attn_kernel after
+// each layer's QKV projection (di_encoder::pair_run, null outside such a call).
+struct PairRun {
+    const int32_t *tt, *ct;  // term_tok, cu_terms (device)
+    const int64_t *cu_sq;    // Mx offset of every document
+    int max_len;
+};
+
 }  // namespace di
 
 struct di_encoder {
@@ -39,6 +47,13 @@ struct di_encoder {
     int64_t cap_rows = 0;  // allocated rows of the GEMM A operands (>= cap_tokens)
     int cap_docs = 0;
     int ld_v = 0;
+    // pairwise head (pairwise_impact_score_encoder, optional): w [2H+1] f32 on the device,
+    // w[0] and the bias on the host; Mx = running maximum of the head-mean probabilities,
+    // T x T per document; uv = the head's two dot products per kept row
+    bool has_pair = false;
+    di::DevBuf pair_w, Mx, uv, cu_sq, cup;
+    float pair_w0 = 0.f, pair_b = 0.f;
+    const di::PairRun *pair_run = nullptr;
     di::DevBuf pinfo;  // di_encode_pairs: (n_tokens, max_len, error bits) of the pack
     di::Timer timer;
 };

@@ -71,6 +71,21 @@ void launch_gather_terms(const float *impact, const int32_t *cu_seq, const int32
                          int n_docs, const int32_t *term_tok, int n_terms, int do_round,
                          float *out, int32_t *err, hipStream_t s);
 
+size_t pair_attn_lds_bytes(int max_len);
+void launch_pair_prep(const int32_t *cu_seq, const int32_t *cu_terms, const int32_t *term_tok,
+                      const int64_t *cu_pairs, int n_docs, int64_t n_terms, int64_t n_pairs,
+                      int max_len, int64_t *cu_sq, int32_t *err, hipStream_t s);
+void launch_pair_attn(const void *qk, bool split, const int32_t *cu_seq, const int32_t *cu_terms,
+                      const int32_t *term_tok, const int64_t *cu_sq, int n_docs, int max_len,
+                      int H, float *Mx, const int32_t *err, hipStream_t s);
+void launch_pair_score(const void *src, int src_mode, const int32_t *cu_seq,
+                       const int32_t *cu_terms, const int32_t *term_tok,
+                       const int64_t *cu_pairs, const int64_t *cu_sq, int n_docs,
+                       int64_t n_terms, int64_t n_pairs, int H, const float *gamma,
+                       const float *beta, float eps, const float *w, float w0, float bias,
+                       const float *Mx, float2 *uv, int do_round, float *out_pair,
+                       float *out_attn, const int32_t *err, hipStream_t s);
+
 }  // namespace di
 
 using namespace di;
@@ -274,9 +289,25 @@ void di::ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms)
     e->cut.reserve((size_t)(n_docs + 1) * 4);
     e->tt.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
     e->err.reserve(16);
+    if (e->has_pair) {  // (Mx grows in di_encode_pairwise, by the batch's sum of T^2)
+        e->uv.reserve((size_t)std::max<int64_t>(n_terms, 1) * 8);
+        e->cu_sq.reserve((size_t)(n_docs + 1) * 8);
+        e->cup.reserve((size_t)(n_docs + 1) * 8);
+    }
 }
 
 namespace {
+
+// di_encode_pairwise: the layer's Q | K rows are in qk -> fold this layer's head-mean
+// probabilities of the term rows into Mx (no-op in every other call)
+void pair_attn_layer(di_encoder *e, const int32_t *d_cu, int n_docs, bool timing,
+                     hipStream_t s) {
+    const PairRun *r = e->pair_run;
+    if (!r) return;
+    TimedLaunch tl(e->timer, timing, "pair_attn", s);
+    launch_pair_attn(e->qk.p, e->split, d_cu, r->ct, r->tt, r->cu_sq, n_docs, r->max_len,
+                     e->cfg.hidden, e->Mx.as<float>(), e->err.as<int32_t>(), s);
+}
 
 template <typename T>
 void forward(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_docs, int64_t M,
@@ -337,6 +368,8 @@ void forward(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_doc
                 TimedLaunch tl(e->timer, timing, "gemm_qkv", s);
                 launch_gemm<T>(EPI_QKV, g, s);
             }
+            if constexpr (std::is_same<T, float>::value)
+                pair_attn_layer(e, d_cu, n_docs, timing, s);
             {
                 TimedLaunch tl(e->timer, timing, "attention", s);
                 launch_attention<T>(e->qk.as<T>(), e->vt.as<T>(), d_cu, n_docs, max_len, H,
@@ -531,6 +564,7 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
                                          6 * (int64_t)H, e->qk.as<bf16>(), s);
             }
         }
+        if (sp) pair_attn_layer(e, d_cu, n_docs, timing, s);
         {
             TimedLaunch tl(e->timer, timing, "attention", s);
             if (sp)
@@ -671,6 +705,7 @@ void forward_split(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int
         const bool prune = last && d_tt != nullptr;
         const int64_t Mr = prune ? n_terms : M;  // rows from here on
         bf16 *Xr = X;                             // the O GEMM's residual rows
+        pair_attn_layer(e, d_cu, n_docs, timing, s);
         {
             TimedLaunch tl(e->timer, timing, "attention", s);
             launch_attention_x3(e->qk.as<bf16>(), d_cu, n_docs, H, ctx, s,
@@ -737,6 +772,201 @@ void forward_split(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int
                             last ? e->head_w.as<float>() : nullptr, e->head_b, c.activation,
                             last ? e->impact.as<float>() : nullptr, s);
         }
+    }
+}
+
+// one di_encode_pairwise call's extra arguments (null: plain di_encode)
+struct PairCall {
+    const int64_t *cu_pairs;
+    int64_t n_pairs;
+    float *out_pair, *out_attn;
+};
+
+void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlens, int32_t n_docs,
+                 int64_t n_tokens, int32_t max_len, const int32_t *term_tok,
+                 const int32_t *cu_terms, int64_t n_terms, float *out, uint32_t flags,
+                 const PairCall *pc) {
+    DI_REQUIRE(e && cu_seqlens && out && n_docs >= 0, DI_EINVAL, "bad argument");
+    DeviceScope ds(e->device);
+    const bool dev = flags & DI_F_DEVICE_PTRS;
+    const bool timing = flags & DI_F_TIMING;
+    const bool token_out = !pc && (flags & DI_F_TOKEN_IMPACTS);
+    int64_t n_pairs = pc ? pc->n_pairs : 0, mx_need = 0;
+    hipStream_t s = e->stream;
+    if (!dev) {
+        DI_REQUIRE(cu_seqlens[0] == 0, DI_EINVAL, "cu_seqlens[0] must be 0");
+        int32_t mx = 0;
+        for (int d = 0; d < n_docs; ++d) {
+            int32_t len = cu_seqlens[d + 1] - cu_seqlens[d];
+            DI_REQUIRE(len >= 0, DI_EINVAL, "cu_seqlens not monotone at %d", d);
+            mx = std::max(mx, len);
+        }
+        n_tokens = cu_seqlens[n_docs];
+        max_len = mx;
+        if (!token_out) {
+            DI_REQUIRE(term_tok && cu_terms && cu_terms[0] == 0, DI_EINVAL,
+                       "term arrays required");
+            n_terms = cu_terms[n_docs];
+        }
+        if (pc) {  // the sorted(map_.values()) order, and one slot per 2-combination
+            DI_REQUIRE(pc->cu_pairs && pc->cu_pairs[0] == 0, DI_EINVAL, "cu_pairs required");
+            for (int d = 0; d < n_docs; ++d) {
+                const int64_t T = (int64_t)cu_terms[d + 1] - cu_terms[d];
+                const int32_t len = cu_seqlens[d + 1] - cu_seqlens[d];
+                DI_REQUIRE(T >= 0, DI_EINVAL, "cu_terms not monotone at %d", d);
+                int32_t prev = -1;
+                for (int32_t i = cu_terms[d]; i < cu_terms[d + 1]; ++i) {
+                    DI_REQUIRE(term_tok[i] > prev, DI_EINVAL,
+                               "term_tok must be strictly ascending inside document %d", d);
+                    prev = term_tok[i];
+                }
+                DI_REQUIRE(prev < len, DI_EINVAL,
+                           "a term token index is outside its document");
+                DI_REQUIRE(pc->cu_pairs[d + 1] - pc->cu_pairs[d] == T * (T - 1) / 2,
+                           DI_EINVAL, "cu_pairs: document %d has %lld terms, so %lld pairs",
+                           d, (long long)T, (long long)(T * (T - 1) / 2));
+                mx_need += T * T;
+            }
+            n_pairs = pc->cu_pairs[n_docs];
+        }
+    } else if (pc) {
+        DI_REQUIRE(n_terms >= 0 && n_terms <= n_tokens && n_pairs >= 0, DI_EINVAL,
+                   "n_terms=%lld n_pairs=%lld", (long long)n_terms, (long long)n_pairs);
+        mx_need = n_terms * std::min<int64_t>(n_terms, max_len);  // >= sum of T^2
+    }
+    DI_REQUIRE(n_tokens >= 0 && n_tokens < (1ll << 31), DI_ERANGE, "n_tokens=%lld",
+               (long long)n_tokens);
+    DI_REQUIRE(max_len <= e->cfg.max_positions, DI_ERANGE,
+               "a document has %d tokens > max_positions %d", max_len,
+               e->cfg.max_positions);
+    if (n_docs == 0) return;
+    ensure_workspace(e, n_tokens, n_docs, n_terms);
+    const int32_t *d_ids =
+        (const int32_t *)stage_in(tok_ids, (size_t)n_tokens * 4, dev, e->ids, s);
+    const int32_t *d_cu =
+        (const int32_t *)stage_in(cu_seqlens, (size_t)(n_docs + 1) * 4, dev, e->cu, s);
+    DI_HIP(hipMemsetAsync(e->err.p, 0, 4, s));
+    const int32_t *d_tt = nullptr, *d_cut = nullptr;
+    if (!token_out) {
+        d_tt = (const int32_t *)stage_in(term_tok, (size_t)n_terms * 4, dev, e->tt, s);
+        d_cut = (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, e->cut, s);
+    }
+    // pairwise: check the arrays on the device too (the only check of device
+    // pointers), lay out and clear Mx, and let the forwards call pair_attn_kernel
+    PairRun run{};
+    struct RunScope {
+        di_encoder *e;
+        ~RunScope() { e->pair_run = nullptr; }
+    } run_scope{e};
+    const int64_t *d_cup = nullptr;
+    if (pc) {
+        DI_REQUIRE(pair_attn_lds_bytes(max_len) <= 160 * 1024, DI_ERANGE,
+                   "pairwise: a document of %d tokens exceeds the LDS panel", max_len);
+        DI_REQUIRE(mx_need <= (1ll << 32), DI_ERANGE,
+                   "pairwise: %lld term-pair slots in one batch (limit 2^32)",
+                   (long long)mx_need);
+        e->Mx.reserve((size_t)std::max<int64_t>(mx_need, 1) * 4);
+        d_cup = (const int64_t *)stage_in(pc->cu_pairs, (size_t)(n_docs + 1) * 8, dev, e->cup,
+                                          s);
+        {
+            TimedLaunch tl(e->timer, timing, "pair_prep", s);
+            if (mx_need) DI_HIP(hipMemsetAsync(e->Mx.p, 0, (size_t)mx_need * 4, s));
+            launch_pair_prep(d_cu, d_cut, d_tt, d_cup, n_docs, n_terms, n_pairs, max_len,
+                             e->cu_sq.as<int64_t>(), e->err.as<int32_t>(), s);
+        }
+        run = PairRun{d_tt, d_cut, e->cu_sq.as<int64_t>(), max_len};
+        if (n_pairs > 0) e->pair_run = &run;
+    }
+    // pruned last layer (bf16 folded and bf16x3 paths, term output)
+    const bool prune = !token_out && (e->split || (e->esz == 2 && e->folded)) &&
+                       n_terms <= n_tokens;  // (packed term rows fit the row buffers)
+    if (n_tokens > 0) {
+        if (e->split && !e->folded)
+            forward_split(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
+                          prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
+        else if (e->split)
+            forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
+                           prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
+        else if (e->esz == 2)
+            if (e->folded)
+                forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
+                               prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
+            else
+                forward<bf16>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
+        else
+            forward<float>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
+    }
+    float *d_out = out;
+    DevBuf tmp;
+    if (token_out) {
+        if (dev)
+            DI_HIP(hipMemcpyAsync(out, e->impact.p, (size_t)n_tokens * 4,
+                                  hipMemcpyDeviceToDevice, s));
+        else
+            DI_HIP(hipMemcpyAsync(out, e->impact.p, (size_t)n_tokens * 4,
+                                  hipMemcpyDeviceToHost, s));
+    } else {
+        if (!dev) {
+            tmp.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
+            d_out = tmp.as<float>();
+        }
+        {
+            TimedLaunch tl(e->timer, timing, "gather_terms", s);
+            launch_gather_terms(e->impact.as<float>(), d_cu, d_cut, n_docs, d_tt,
+                                (int)n_terms,
+                                ((flags & DI_F_ROUND3) ? 1 : 0) | (prune && n_tokens > 0 ? 2 : 0),
+                                d_out, e->err.as<int32_t>(), s);
+        }
+        if (!dev && n_terms)
+            DI_HIP(hipMemcpyAsync(out, d_out, (size_t)n_terms * 4, hipMemcpyDeviceToHost,
+                                  s));
+    }
+    DevBuf tmp_pair, tmp_attn;
+    if (pc && n_pairs > 0) {
+        float *d_pair = pc->out_pair, *d_attn = pc->out_attn;
+        if (!dev) {
+            tmp_pair.reserve((size_t)n_pairs * 4);
+            d_pair = tmp_pair.as<float>();
+            if (pc->out_attn) {
+                tmp_attn.reserve((size_t)n_pairs * 4);
+                d_attn = tmp_attn.as<float>();
+            }
+        }
+        // the last layer's pre-LayerNorm rows: f32 at the token rows (fp32), f32 packed
+        // (bf16x3 unfolded) or split rows packed (bf16x3 folded; pruned either way)
+        const int mode = !e->split ? 0 : (e->folded ? 2 : 1);
+        const void *src = mode == 2 ? e->X.p : e->pre.p;
+        const Layer &L = *e->layers.back();
+        {
+            TimedLaunch tl(e->timer, timing, "pair_score", s);
+            launch_pair_score(src, mode, d_cu, d_cut, d_tt, d_cup, e->cu_sq.as<int64_t>(),
+                              n_docs, n_terms, n_pairs, e->cfg.hidden, L.ln2_g.as<float>(),
+                              L.ln2_b.as<float>(), e->cfg.layer_norm_eps,
+                              e->pair_w.as<float>(), e->pair_w0, e->pair_b,
+                              e->Mx.as<float>(), e->uv.as<float2>(),
+                              (flags & DI_F_ROUND3) ? 1 : 0, d_pair, d_attn,
+                              e->err.as<int32_t>(), s);
+        }
+        if (!dev) {
+            DI_HIP(hipMemcpyAsync(pc->out_pair, d_pair, (size_t)n_pairs * 4,
+                                  hipMemcpyDeviceToHost, s));
+            if (pc->out_attn)
+                DI_HIP(hipMemcpyAsync(pc->out_attn, d_attn, (size_t)n_pairs * 4,
+                                      hipMemcpyDeviceToHost, s));
+        }
+    }
+    if (!(flags & DI_F_ASYNC) || !dev) {
+        int32_t err = 0;
+        DI_HIP(hipMemcpyAsync(&err, e->err.p, 4, hipMemcpyDeviceToHost, s));
+        DI_HIP(hipStreamSynchronize(s));
+        e->timer.resolve();
+        DI_REQUIRE(!(err & 1), DI_EINVAL,
+                   "a token id is outside the vocabulary or a position exceeds the table");
+        DI_REQUIRE(!(err & 2), DI_EINVAL, "a term token index is outside its document");
+        DI_REQUIRE(!(err & 4), DI_EINVAL,
+                   "term_tok must be strictly ascending inside each document, within it");
+        DI_REQUIRE(!(err & 8), DI_EINVAL,
+                   "cu_pairs must hold T (T - 1) / 2 pairs per document");
     }
 }
 
@@ -898,6 +1128,21 @@ int di_encoder_create(const di_encoder_cfg *cfg, const di_tensor *w, int32_t n_w
             e->head_sw = (float)sw;
             e->head_cw = (float)cw;
         }
+        // DeepPairwiseImpact's second head (pairwise_impact.py:13-16): both tensors or neither
+        {
+            const bool pw = byname.count("pairwise_impact_score_encoder.0.weight") != 0;
+            const bool pb = byname.count("pairwise_impact_score_encoder.0.bias") != 0;
+            DI_REQUIRE(pw == pb, DI_EINVAL,
+                       "pairwise_impact_score_encoder: weight and bias come together");
+            if (pw) {
+                const HostTensor *w2 =
+                    get("pairwise_impact_score_encoder.0.weight", {1, 2 * H + 1});
+                upload(e->pair_w, {w2}, 0, true, 4);
+                e->pair_w0 = w2->at(0);
+                e->pair_b = get("pairwise_impact_score_encoder.0.bias", {1})->at(0);
+                e->has_pair = true;
+            }
+        }
         // strict, as ModelCheckpoint.load -> load_state_dict (checkpoint.py:117)
         for (auto &kv : byname)
             DI_REQUIRE(used.count(kv.first), DI_EINVAL, "unexpected weight %s",
@@ -910,98 +1155,26 @@ int di_encode(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlens, 
               int64_t n_tokens, int32_t max_len, const int32_t *term_tok, const int32_t *cu_terms,
               int64_t n_terms, float *out, uint32_t flags) {
     return guard([&] {
-        DI_REQUIRE(e && cu_seqlens && out && n_docs >= 0, DI_EINVAL, "bad argument");
-        DeviceScope ds(e->device);
-        const bool dev = flags & DI_F_DEVICE_PTRS;
-        const bool timing = flags & DI_F_TIMING;
-        const bool token_out = flags & DI_F_TOKEN_IMPACTS;
-        hipStream_t s = e->stream;
-        if (!dev) {
-            DI_REQUIRE(cu_seqlens[0] == 0, DI_EINVAL, "cu_seqlens[0] must be 0");
-            int32_t mx = 0;
-            for (int d = 0; d < n_docs; ++d) {
-                int32_t len = cu_seqlens[d + 1] - cu_seqlens[d];
-                DI_REQUIRE(len >= 0, DI_EINVAL, "cu_seqlens not monotone at %d", d);
-                mx = std::max(mx, len);
-            }
-            n_tokens = cu_seqlens[n_docs];
-            max_len = mx;
-            if (!token_out) {
-                DI_REQUIRE(term_tok && cu_terms && cu_terms[0] == 0, DI_EINVAL,
-                           "term arrays required");
-                n_terms = cu_terms[n_docs];
-            }
-        }
-        DI_REQUIRE(n_tokens >= 0 && n_tokens < (1ll << 31), DI_ERANGE, "n_tokens=%lld",
-                   (long long)n_tokens);
-        DI_REQUIRE(max_len <= e->cfg.max_positions, DI_ERANGE,
-                   "a document has %d tokens > max_positions %d", max_len,
-                   e->cfg.max_positions);
-        if (n_docs == 0) return;
-        ensure_workspace(e, n_tokens, n_docs, n_terms);
-        const int32_t *d_ids =
-            (const int32_t *)stage_in(tok_ids, (size_t)n_tokens * 4, dev, e->ids, s);
-        const int32_t *d_cu =
-            (const int32_t *)stage_in(cu_seqlens, (size_t)(n_docs + 1) * 4, dev, e->cu, s);
-        DI_HIP(hipMemsetAsync(e->err.p, 0, 4, s));
-        const int32_t *d_tt = nullptr, *d_cut = nullptr;
-        if (!token_out) {
-            d_tt = (const int32_t *)stage_in(term_tok, (size_t)n_terms * 4, dev, e->tt, s);
-            d_cut = (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, e->cut, s);
-        }
-        // pruned last layer (bf16 folded and bf16x3 paths, term output)
-        const bool prune = !token_out && (e->split || (e->esz == 2 && e->folded)) &&
-                           n_terms <= n_tokens;  // (packed term rows fit the row buffers)
-        if (n_tokens > 0) {
-            if (e->split && !e->folded)
-                forward_split(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
-                              prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
-            else if (e->split)
-                forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
-                               prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
-            else if (e->esz == 2)
-                if (e->folded)
-                    forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
-                                   prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
-                else
-                    forward<bf16>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
-            else
-                forward<float>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
-        }
-        float *d_out = out;
-        DevBuf tmp;
-        if (token_out) {
-            if (dev)
-                DI_HIP(hipMemcpyAsync(out, e->impact.p, (size_t)n_tokens * 4,
-                                      hipMemcpyDeviceToDevice, s));
-            else
-                DI_HIP(hipMemcpyAsync(out, e->impact.p, (size_t)n_tokens * 4,
-                                      hipMemcpyDeviceToHost, s));
-        } else {
-            if (!dev) {
-                tmp.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
-                d_out = tmp.as<float>();
-            }
-            {
-                TimedLaunch tl(e->timer, timing, "gather_terms", s);
-                launch_gather_terms(e->impact.as<float>(), d_cu, d_cut, n_docs, d_tt,
-                                    (int)n_terms,
-                                    ((flags & DI_F_ROUND3) ? 1 : 0) | (prune && n_tokens > 0 ? 2 : 0),
-                                    d_out, e->err.as<int32_t>(), s);
-            }
-            if (!dev && n_terms)
-                DI_HIP(hipMemcpyAsync(out, d_out, (size_t)n_terms * 4, hipMemcpyDeviceToHost,
-                                      s));
-        }
-        if (!(flags & DI_F_ASYNC) || !dev) {
-            int32_t err = 0;
-            DI_HIP(hipMemcpyAsync(&err, e->err.p, 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipStreamSynchronize(s));
-            e->timer.resolve();
-            DI_REQUIRE(!(err & 1), DI_EINVAL,
-                       "a token id is outside the vocabulary or a position exceeds the table");
-            DI_REQUIRE(!(err & 2), DI_EINVAL, "a term token index is outside its document");
-        }
+        encode_impl(e, tok_ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
+                    n_terms, out, flags, nullptr);
+    });
+}
+
+int di_encode_pairwise(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlens,
+                       int32_t n_docs, int64_t n_tokens, int32_t max_len,
+                       const int32_t *term_tok, const int32_t *cu_terms, int64_t n_terms,
+                       const int64_t *cu_pairs, int64_t n_pairs, float *out_single,
+                       float *out_pair, float *out_pair_attn, uint32_t flags) {
+    return guard([&] {
+        DI_REQUIRE(e && cu_pairs && out_pair, DI_EINVAL, "bad argument");
+        DI_REQUIRE(e->has_pair, DI_EINVAL,
+                   "the encoder was created without pairwise_impact_score_encoder");
+        DI_REQUIRE(e->cfg.precision != DI_PREC_BF16, DI_EINVAL,
+                   "pairwise impacts need precision fp32 or bf16x3 (bf16 is not fp32-faithful)");
+        DI_REQUIRE(!(flags & DI_F_TOKEN_IMPACTS), DI_EINVAL, "pairwise: term output only");
+        const PairCall pc{cu_pairs, n_pairs, out_pair, out_pair_attn};
+        encode_impl(e, tok_ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
+                    n_terms, out_single, flags, &pc);
     });
 }
 

@@ -186,10 +186,52 @@ class DeviceEncoder:
         n = int(cu[-1]) if token_impacts else int(ct[-1])
         return out[:n]
 
+    def encode_pairwise(self, ids, cu_seqlens, term_tok, cu_terms, round3=False,
+                        attentions=False, timing=False, cu_pairs=None):
+        """di_encode_pairwise: the term impacts of encode_packed and, for every
+        2-combination of a document's terms, DeepPairwiseImpact's pair score
+        (pairwise_impact.py:20-95).  term_tok strictly ascending inside each document.
+        Host arrays in -> (single float32 [n_terms], pair float32 [n_pairs], cu_pairs int64
+        [n_docs + 1][, attn float32 [n_pairs]]); document d's pairs are in
+        itertools.combinations order at cu_pairs[d].  (cu_pairs: computed from cu_terms
+        unless given; the library checks it either way.)"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, np.int32)
+        tt = np.ascontiguousarray(term_tok, np.int32)
+        ct = np.ascontiguousarray(cu_terms, np.int32)
+        n_docs = len(cu) - 1
+        T = np.diff(ct.astype(np.int64))
+        if cu_pairs is None:
+            cu_pairs = np.zeros(n_docs + 1, np.int64)
+            cu_pairs[1:] = np.cumsum(T * (T - 1) // 2)
+        cu_pairs = np.ascontiguousarray(cu_pairs, np.int64)
+        n_terms, n_pairs = int(ct[-1]), max(int(cu_pairs[-1]), 0)
+        single = np.zeros(max(1, n_terms), np.float32)
+        pair = np.zeros(max(1, n_pairs), np.float32)
+        attn = np.zeros(max(1, n_pairs), np.float32) if attentions else None
+        flags = (DI_F_ROUND3 if round3 else 0) | (_lib.DI_F_TIMING if timing else 0)
+        if tt.size == 0:
+            tt = np.zeros(1, np.int32)
+        if ids.size == 0:
+            ids = np.zeros(1, np.int32)
+        check(lib().di_encode_pairwise(self._h, ptr(ids), ptr(cu), n_docs, 0, 0, ptr(tt), ptr(ct),
+                                       0, ptr(cu_pairs), 0, ptr(single), ptr(pair), ptr(attn),
+                                       flags))
+        out = (single[:n_terms], pair[:n_pairs], cu_pairs)
+        return out + (attn[:n_pairs],) if attentions else out
+
     def encode_device(self, ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
                       n_terms, out, flags=_lib.DI_F_DEVICE_PTRS):
         check(lib().di_encode(self._h, ptr(ids), ptr(cu_seqlens), n_docs, n_tokens, max_len,
                               ptr(term_tok), ptr(cu_terms), n_terms, ptr(out), flags))
+
+    def encode_pairwise_device(self, ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok,
+                               cu_terms, n_terms, cu_pairs, n_pairs, out_single, out_pair,
+                               out_attn=None, flags=_lib.DI_F_DEVICE_PTRS):
+        check(lib().di_encode_pairwise(self._h, ptr(ids), ptr(cu_seqlens), n_docs, n_tokens,
+                                       max_len, ptr(term_tok), ptr(cu_terms), n_terms,
+                                       ptr(cu_pairs), n_pairs, ptr(out_single), ptr(out_pair),
+                                       ptr(out_attn), flags))
 
     def encode_pairs(self, doc_tok, doc_off, qry_tok, qry_off, pair_doc, pair_qry, fmt,
                      out=None, timing=False):

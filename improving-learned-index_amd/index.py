@@ -8,6 +8,9 @@ reference src/deep_impact/index.py:12-68).
 Same flags as the reference plus --tokenizer_path / --max_length / --precision /
 --device / --variant (the reference hard-wires a hub tokenizer and 512 tokens).
 Output bytes are those of the reference (one line per input line, in order).
+--pairwise loads the checkpoint as DeepPairwiseImpact (models/pairwise_impact.py) and adds
+each passage's 't1|t2' pair entries, the line sorted by score (the call the reference's
+indexer.py:49-54 holds in a comment).
 Multi-GPU: --doc_range start:end encodes one doc-id shard; concatenating the
 shard outputs in order gives the single-GPU file.  Under torchrun
 (--nproc-per-node N) every rank encodes doc-id shard r on its GPU and rank 0 joins
@@ -26,7 +29,7 @@ from pathlib import Path
 from . import parallel
 from .datasets import COLLECTION_TYPES, CollectionParser
 from .indexer import Indexer, TokenizerPool, pool_supported, resolve_tokenizer
-from .models import DeepImpact
+from .models import DeepImpact, DeepPairwiseImpact
 
 BATCH_SIZE = 32  # src/utils/defaults.py:15
 
@@ -37,8 +40,9 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
         num_processes=8, process_batch_size=50 * BATCH_SIZE, model_batch_size=BATCH_SIZE,
         tokenizer_path=None, max_length=None, precision="bf16x3", device=0, variant="xlmr",
         doc_range=None, pairwise=False, first_shard=True):
-    if pairwise:
-        raise NotImplementedError("DeepPairwiseImpact is outside this build (SURVEY §8f F4)")
+    # --pairwise: DeepPairwiseImpact through the same Indexer (its lines add the
+    # 't1|t2' entries and are sorted by score, pairwise_impact.py:98-129)
+    model_cls = DeepPairwiseImpact if pairwise else DeepImpact
     start = time.time()
     # the tokenizer workers start before the GPU is initialised (DeepImpact.load)
     tok = resolve_tokenizer(model_checkpoint_path, tokenizer_path)
@@ -47,9 +51,9 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
         pool = TokenizerPool(num_processes, tok, max_length or DeepImpact.max_length,
                              "bert_legacy" if variant == "bert" else "word_ids")
     try:
-        model = DeepImpact.load(model_checkpoint_path, tokenizer_path=tokenizer_path,
-                                precision=precision, device=device, variant=variant,
-                                max_length=max_length)
+        model = model_cls.load(model_checkpoint_path, tokenizer_path=tokenizer_path,
+                               precision=precision, device=device, variant=variant,
+                               max_length=max_length)
         indexer = Indexer(model, model_batch_size=model_batch_size,
                           num_processes=num_processes, pool=pool)
         return _index_file(indexer, collection_path, collection_type, output_file_path,

@@ -564,6 +564,195 @@ class DeepImpactCrossEncoder(DeepImpact):
         return torch.from_numpy(np.array(out, np.float32)).unsqueeze(-1)
 
 
+# --------------------------------------------------------------------------- pairwise
+def round3(x):
+    """numpy's round(np.float32, 3) (indexer.py:64) on an array: fl32(rint(fl32(x * 1000))
+    / 1000), what DI_F_ROUND3 applies on the device."""
+    x = np.asarray(x, np.float32)
+    return (np.rint(x * np.float32(1000.0)) / np.float32(1000.0)).astype(np.float32)
+
+
+def pair_index(a, b, T):
+    """Position of the pair (a, b), a < b < T, in itertools.combinations(range(T), 2)."""
+    return a * (2 * T - a - 1) // 2 + (b - a - 1)
+
+
+def pair_ab(j, T):
+    """Inverse of pair_index on int64 arrays: (a, b) of the positions j of documents with
+    T terms each (T broadcast against j)."""
+    j = np.asarray(j, np.int64)
+    T = np.broadcast_to(np.asarray(T, np.int64), j.shape)
+    s = (2 * T - 1).astype(np.float64)
+    a = ((s - np.sqrt(s * s - 8.0 * j)) * 0.5).astype(np.int64)
+    a = np.clip(a, 0, np.maximum(T - 2, 0))
+    a -= pair_index(a, a + 1, T) > j          # (the float root may be one off either way)
+    a += pair_index(a + 1, a + 2, T) <= j
+    return a, a + 1 + (j - pair_index(a, a + 1, T))
+
+
+def pairwise_entries(tt, ct, single, pair, cu_pairs):
+    """The order of DeepPairwiseImpact.compute_term_impacts (pairwise_impact.py:98-129) on
+    packed arrays: per document its terms in map order, then the pairs whose score does
+    not round to 0.000, in combination order over the terms sorted by token index, the
+    whole list sorted by raw score descending (stable: ties keep that order).
+    tt / ct: the terms' token index in map order and their offsets; single [n_terms] in
+    that order; pair [n_pairs] in combination order of the sorted terms.
+    Returns (cu_out int64 [n_docs + 1], is_pair bool [n_out], first int64 [n_out], second
+    int64 [n_out], score float32 [n_out]): entry e is term `first` (a global term index)
+    or the pair (first, second)."""
+    tt, ct = np.asarray(tt, np.int64), np.asarray(ct, np.int64)
+    single, pair = np.asarray(single, np.float32), np.asarray(pair, np.float32)
+    cu_pairs = np.asarray(cu_pairs, np.int64)
+    n_docs, n_terms = len(ct) - 1, int(ct[-1])
+    T = np.diff(ct)
+    tdoc = np.repeat(np.arange(n_docs), T)
+    # rank r of document d's sorted terms -> global term index
+    by_tok = np.lexsort((tt[:n_terms], tdoc))
+    keep = np.flatnonzero(round3(pair) != 0)
+    pdoc = np.searchsorted(cu_pairs, keep, side="right") - 1
+    j = keep - cu_pairs[pdoc]
+    a, b = pair_ab(j, T[pdoc])
+    doc = np.concatenate([tdoc, pdoc])
+    score = np.concatenate([single[:n_terms], pair[keep]])
+    pos = np.concatenate([np.arange(n_terms) - ct[tdoc], T[pdoc] + j])
+    order = np.lexsort((pos, -score, doc))
+    first = np.concatenate([np.arange(n_terms), by_tok[ct[pdoc] + a]])[order]
+    second = np.concatenate([np.zeros(n_terms, np.int64), by_tok[ct[pdoc] + b]])[order]
+    cu_out = np.zeros(n_docs + 1, np.int64)
+    cu_out[1:] = np.cumsum(np.bincount(doc, minlength=n_docs))
+    return cu_out, (order >= n_terms), first, second, score[order]
+
+
+class DeepPairwiseImpact(DeepImpact):
+    """DeepImpact (RoBERTa body, ReLU head) plus the pair head of
+    src/deep_impact/models/pairwise_impact.py: every 2-combination of a document's kept
+    terms gets relu(Linear(2H+1)([attn, h_a, h_b])) with attn the largest head-mean
+    attention probability between the two first tokens over layers and directions.  The
+    reference's Indexer holds the pairwise call in a comment (indexer.py:49-54); this
+    class runs what that block and the model define."""
+
+    @classmethod
+    def load(cls, checkpoint_path=None, *, config: Optional[EncoderConfig] = None,
+             tokenizer_path=None, precision: str = "bf16x3", device: int = 0,
+             variant: str = "xlmr", max_length: Optional[int] = None) -> "DeepPairwiseImpact":
+        """DeepImpact.load with the ReLU head (original.py:41-48) and the two
+        pairwise_impact_score_encoder tensors, which the checkpoint must hold."""
+        sd, cfg = _load_weights(checkpoint_path, config, variant)
+        if config is None:
+            cfg.activation = "relu"
+        if "pairwise_impact_score_encoder.0.weight" not in sd:
+            raise KeyError("the checkpoint has no pairwise_impact_score_encoder")
+        enc = DeviceEncoder(sd, cfg, precision=precision, device=device)
+        tok = tokenizer_path
+        if tok is None and checkpoint_path is not None and Path(checkpoint_path).is_dir() and \
+                (Path(checkpoint_path) / "tokenizer.json").exists():
+            tok = Path(checkpoint_path) / "tokenizer.json"
+        model = cls(enc, tok, max_length)
+        cls.term_mapping = "bert_legacy" if variant == "bert" else "word_ids"
+        return model
+
+    # ------------------------------------------------------------------ forward
+    def __call__(self, input_ids, attention_mask, token_type_ids=None, pairwise_indices=None):
+        """Reference forward protocol (pairwise_impact.py:20-42): padded [B, S] batch and
+        per document a list of (token a, token b) pairs, a < b, in -> (per-token impacts
+        [B, S, 1], per document the pair scores [n, 1], per document the pair attentions
+        [n, 1]), float32 host tensors."""
+        import torch
+
+        if pairwise_indices is None:
+            raise TypeError("pairwise_indices is required")
+        single = DeepImpact.__call__(self, input_ids, attention_mask, token_type_ids)
+        ids = np.asarray(input_ids.cpu() if hasattr(input_ids, "cpu") else input_ids)
+        mask = np.asarray(attention_mask.cpu() if hasattr(attention_mask, "cpu")
+                          else attention_mask).astype(bool)
+        cu = np.zeros(len(ids) + 1, np.int32)
+        cu[1:] = np.cumsum(mask.sum(1))
+        toks = [np.unique(np.asarray(p, np.int64).reshape(-1, 2)) for p in pairwise_indices]
+        ct = np.zeros(len(ids) + 1, np.int32)
+        ct[1:] = np.cumsum([len(t) for t in toks])
+        tt = np.concatenate(toks).astype(np.int32) if toks else np.zeros(0, np.int32)
+        _, pair, cu_pairs, attn = self.encoder.encode_pairwise(
+            ids[mask].astype(np.int32), cu, tt, ct, attentions=True)
+        scores, attns = [], []
+        for d, p in enumerate(pairwise_indices):
+            p = np.asarray(p, np.int64).reshape(-1, 2)
+            if (p[:, 0] >= p[:, 1]).any():
+                raise ValueError("pairwise_indices: every pair must be (a, b) with a < b")
+            a, b = np.searchsorted(toks[d], p[:, 0]), np.searchsorted(toks[d], p[:, 1])
+            at = cu_pairs[d] + pair_index(a, b, len(toks[d]))
+            scores.append(torch.from_numpy(pair[at].reshape(-1, 1).copy()))
+            attns.append(torch.from_numpy(attn[at].reshape(-1, 1).copy()))
+        return single, scores, attns
+
+    @staticmethod
+    def compute_term_impacts(documents_term_to_token_index_map: List[Dict[str, int]],
+                             outputs) -> List[List[Tuple[str, float]]]:
+        """pairwise_impact.py:98-129: outputs = (per-token impacts [B, S(, 1)], per document
+        the pair scores in combination order of its terms sorted by token index[, the
+        attentions])."""
+        maps = documents_term_to_token_index_map
+        imp, pairs = outputs[0], outputs[1]
+        if hasattr(imp, "detach"):
+            imp = imp.detach().cpu().numpy()
+        imp = np.asarray(imp)
+        if imp.ndim == 3:
+            imp = imp[..., 0]
+        pairs = [np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x,
+                            np.float32).reshape(-1) for x in pairs]
+        terms = [t for m in maps for t in m]
+        tt = np.fromiter((i for m in maps for i in m.values()), np.int64, count=len(terms))
+        ct = np.zeros(len(maps) + 1, np.int64)
+        ct[1:] = np.cumsum([len(m) for m in maps])
+        single = np.array([imp[d][i] for d, m in enumerate(maps) for i in m.values()], np.float32)
+        cu_pairs = np.zeros(len(maps) + 1, np.int64)
+        cu_pairs[1:] = np.cumsum([len(x) for x in pairs])
+        pair = np.concatenate(pairs) if pairs else np.zeros(0, np.float32)
+        names, score, cu_out = _pairwise_named(terms, tt, ct, single, pair, cu_pairs)
+        return [list(zip(names[cu_out[d]:cu_out[d + 1]], score[cu_out[d]:cu_out[d + 1]]))
+                for d in range(len(maps))]
+
+    def _encode_entries(self, ids, cu, terms, tt, ct, round3_):
+        """Device call on a packed batch -> (names, scores, cu_out) of its lines."""
+        tt, ct = np.asarray(tt, np.int32), np.asarray(ct, np.int32)
+        n_terms = int(ct[-1])
+        tdoc = np.repeat(np.arange(len(ct) - 1), np.diff(ct))
+        by_tok = np.lexsort((tt[:n_terms], tdoc))  # (the identity for first-occurrence maps)
+        s_sorted, pair, cu_pairs = self.encoder.encode_pairwise(ids, cu, tt[:n_terms][by_tok], ct)
+        single = np.empty(n_terms, np.float32)
+        single[by_tok] = s_sorted
+        names, score, cu_out = _pairwise_named(terms, tt, ct, single, pair, cu_pairs)
+        return names, (round3(score) if round3_ else score), cu_out
+
+    def encode_packed_terms(self, packed, round3=False):
+        ids, cu, terms, tt, ct = packed
+        names, score, cu_out = self._encode_entries(ids, cu, terms, tt, ct, round3)
+        return [list(zip(names[cu_out[d]:cu_out[d + 1]], score[cu_out[d]:cu_out[d + 1]]))
+                for d in range(len(ct) - 1)]
+
+    def encode_packed_impacts(self, packed):
+        ids, cu, blob, term_off, tt, ct = packed
+        terms = [blob[term_off[i]:term_off[i + 1]].decode("utf-8")
+                 for i in range(len(term_off) - 1)]
+        names, score, cu_out = self._encode_entries(ids, cu, terms, tt, ct, True)
+
+        def fmt():
+            enc = [t.encode("utf-8") for t in names]
+            off = np.zeros(len(enc) + 1, np.int64)
+            if enc:
+                off[1:] = np.cumsum([len(b) for b in enc])
+            return _lib.format_impact_lines_packed(b"".join(enc), off, score, cu_out)
+
+        return fmt
+
+
+def _pairwise_named(terms, tt, ct, single, pair, cu_pairs):
+    """pairwise_entries with the entries' names: the term, or f'{term1}|{term2}'."""
+    cu_out, is_pair, first, second, score = pairwise_entries(tt, ct, single, pair, cu_pairs)
+    names = [f"{terms[f]}|{terms[s]}" if p else terms[f]
+             for p, f, s in zip(is_pair.tolist(), first.tolist(), second.tolist())]
+    return names, score, cu_out
+
+
 # --------------------------------------------------------------------------- weights
 def _load_weights(checkpoint_path, config, variant):
     import torch

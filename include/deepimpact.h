@@ -263,7 +263,9 @@ typedef struct di_tensor {
 /* Replaces DeepImpact.load + .to(cuda).eval() (xlmr_original.py:191-203,
  * indexer.py:22-24).  Strict like load_state_dict (checkpoint.py:117): a missing
  * or unexpected key is DI_EINVAL; "embeddings.position_ids" and "pooler.*" are
- * ignored.  Head dim must be 64; hidden <= 1024. */
+ * ignored.  Head dim must be 64; hidden <= 1024.  Optional: the pair head of
+ * DeepPairwiseImpact, "pairwise_impact_score_encoder.0.weight" / ".0.bias" (see
+ * di_encode_pairwise). */
 int di_encoder_create(const di_encoder_cfg *cfg, const di_tensor *weights, int32_t n_weights,
                       int device, di_encoder **out);
 
@@ -279,6 +281,35 @@ int di_encoder_create(const di_encoder_cfg *cfg, const di_tensor *weights, int32
 int di_encode(di_encoder *enc, const int32_t *tok_ids, const int32_t *cu_seqlens, int32_t n_docs,
               int64_t n_tokens, int32_t max_len, const int32_t *term_tok, const int32_t *cu_terms,
               int64_t n_terms, float *out, uint32_t flags);
+
+/* Replaces DeepPairwiseImpact.forward (src/deep_impact/models/pairwise_impact.py:20-95)
+ * with pairwise_indices = combinations(sorted(map_.values()), 2) per document -- the
+ * call src/deep_impact/indexing/indexer.py:49-54 holds in a comment -- for a batch.
+ * The encoder must have been created with the two optional tensors
+ * "pairwise_impact_score_encoder.0.weight" [1, 2H+1] and ".0.bias" [1] (one without the
+ * other, or a wrong shape, fails di_encoder_create with DI_EINVAL; without them
+ * everything else is unchanged) in precision fp32 or bf16x3: a bf16 encoder, or one
+ * without the pair head, gets DI_EINVAL here.
+ * tok_ids .. n_terms: as di_encode; term_tok must be strictly ascending inside each
+ * document (the sorted order), else DI_EINVAL.  cu_pairs[n_docs+1] (int64):
+ * cu_pairs[d+1] - cu_pairs[d] = T_d (T_d - 1) / 2 for the T_d terms of document d, else
+ * DI_EINVAL; n_pairs is required with DI_F_DEVICE_PTRS (then both checks run on the
+ * device and are reported with di_encode's error bits).
+ * out_single[n_terms]: exactly what di_encode writes for the same arrays.
+ * out_pair[n_pairs]: for the terms a < b (positions within the document's term list)
+ *   relu(w[0] attn(a,b) + w[1:H+1] h_a + w[H+1:2H+1] h_b + bias),
+ *   attn(a,b) = max over layers of max(mean_h P[h,a,b], mean_h P[h,b,a]),
+ * at cu_pairs[d] + a (2 T_d - a - 1) / 2 + (b - a - 1): itertools.combinations order.
+ * out_pair_attn[n_pairs] (may be NULL): attn(a,b), the forward's third result.
+ * Flags: DI_F_ROUND3 (singles and pairs), DI_F_DEVICE_PTRS, DI_F_ASYNC, DI_F_TIMING
+ * ("pair_attn", "pair_score", "pair_prep" beside di_encode's kernels).  Limits
+ * (DI_ERANGE): documents of up to ~1200 tokens (the 160 KiB LDS panel of 16 term rows),
+ * sum of T_d^2 over the batch <= 2^32. */
+int di_encode_pairwise(di_encoder *enc, const int32_t *tok_ids, const int32_t *cu_seqlens,
+                       int32_t n_docs, int64_t n_tokens, int32_t max_len,
+                       const int32_t *term_tok, const int32_t *cu_terms, int64_t n_terms,
+                       const int64_t *cu_pairs, int64_t n_pairs, float *out_single,
+                       float *out_pair, float *out_pair_attn /* may be NULL */, uint32_t flags);
 int di_encoder_reserve(di_encoder *enc, int64_t max_tokens, int32_t max_docs, int64_t max_terms);
 int di_encoder_set_stream(di_encoder *enc, void *hip_stream);
 int di_encoder_sync(di_encoder *enc);
