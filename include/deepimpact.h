@@ -303,8 +303,10 @@ int di_encode(di_encoder *enc, const int32_t *tok_ids, const int32_t *cu_seqlens
  * out_pair_attn[n_pairs] (may be NULL): attn(a,b), the forward's third result.
  * Flags: DI_F_ROUND3 (singles and pairs), DI_F_DEVICE_PTRS, DI_F_ASYNC, DI_F_TIMING
  * ("pair_attn", "pair_score", "pair_prep" beside di_encode's kernels).  Limits
- * (DI_ERANGE): documents of up to ~1200 tokens (the 160 KiB LDS panel of 16 term rows),
- * sum of T_d^2 over the batch <= 2^32. */
+ * (DI_ERANGE): documents of up to 1232 tokens -- the LDS of the 16 term rows' score
+ * panel, head sums and term columns, sized for T = n terms of the longest document's n
+ * tokens: (16 (16 ceil(n / 16) + 4) + 17 n) 4 bytes <= 160 KiB, which 1232 meets and
+ * 1233 does not; sum of T_d^2 over the batch <= 2^32. */
 int di_encode_pairwise(di_encoder *enc, const int32_t *tok_ids, const int32_t *cu_seqlens,
                        int32_t n_docs, int64_t n_tokens, int32_t max_len,
                        const int32_t *term_tok, const int32_t *cu_terms, int64_t n_terms,

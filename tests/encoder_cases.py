@@ -28,20 +28,30 @@ PEAKED_LENS = [512, 385, 384, 257, 256, 65, 64, 33, 32, 17, 1]
 SEED = 7
 
 
-def shapes(hidden, intermediate, vocab=1024, layers=2):
+def shapes(hidden, intermediate, vocab=1024, layers=2, max_positions=None, type_vocab=None):
     """(state_dict_shapes, config) of the xlm-roberta-base fixture with 768 -> hidden,
     3072 -> intermediate, 250002 -> vocab, layers >= `layers` dropped and
-    num_attention_heads = hidden // 64."""
+    num_attention_heads = hidden // 64; max_positions / type_vocab: the rows of the
+    position and token-type tables (the fixture's 514 and 1 unless given)."""
     fx = json.loads((GOLDEN / "encoder_xlmr_base.json").read_text())
     sub = {768: hidden, 3072: intermediate, 250002: vocab}
+    rows = {"bert.embeddings.position_embeddings.weight": max_positions,
+            "bert.embeddings.token_type_embeddings.weight": type_vocab}
     out = []
     for k, shape, dtype in fx["state_dict_shapes"]:
         if ".layer." in k and int(k.split(".layer.")[1].split(".")[0]) >= layers:
             continue
-        out.append((k, [sub.get(d, d) for d in shape], dtype))
+        shape = [sub.get(d, d) for d in shape]
+        if rows.get(k) is not None:
+            shape[0] = rows[k]
+        out.append((k, shape, dtype))
     cfg = dict(fx["config"])
     cfg.update(hidden_size=hidden, intermediate_size=intermediate, vocab_size=vocab,
                num_hidden_layers=layers, num_attention_heads=hidden // 64)
+    if max_positions is not None:
+        cfg["max_position_embeddings"] = max_positions
+    if type_vocab is not None:
+        cfg["type_vocab_size"] = type_vocab
     return out, cfg
 
 
