@@ -23,6 +23,10 @@ DI_F_LISTS_MAJOR = 0x8
 DI_SHORT_QUERY_TERMS = 256  # longer queries: wide merge keys (include/deepimpact.h)
 DI_MAX_QUERY_TERMS = 4096
 DI_MAX_TOPK = 4096
+DI_PAIR_ORDER_LDS_KEYS = 16384  # entries one workgroup orders in LDS (include/deepimpact.h)
+DI_PAIR_ORDER_MAX_TERMS = 2047
+DI_F_ROUND3 = 0x10
+DI_ERANGE = -4
 
 _ERRNAMES = {-1: "DI_EINVAL", -2: "DI_ENOMEM", -3: "DI_EHIP", -4: "DI_ERANGE",
              -5: "DI_ENODEV", -6: "DI_EIO", -7: "DI_EFORMAT"}
@@ -97,6 +101,10 @@ SIGNATURES = {
     "di_encode": (ctypes.c_int, [P, P, P, I32, I64, I32, P, P, I64, P, U32]),
     "di_encode_pairwise": (ctypes.c_int, [P, P, P, I32, I64, I32, P, P, I64, P, I64, P, P, P,
                                           U32]),
+    "di_pairwise_order": (ctypes.c_int, [P, P, P, P, P, I32, I64, I64, P, P, P, P, I64, P,
+                                         ctypes.c_int, P, U32]),
+    "di_encode_pairwise_entries": (ctypes.c_int, [P, P, P, I32, I64, I32, P, P, I64, P, I64, P,
+                                                  P, P, P, P, I64, P, U32]),
     "di_encoder_reserve": (ctypes.c_int, [P, I64, I32, I64]),
     "di_encoder_set_stream": (ctypes.c_int, [P, P]),
     "di_encoder_sync": (ctypes.c_int, [P]),
@@ -110,6 +118,7 @@ SIGNATURES = {
     "di_quantize_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, I32,
                                         ctypes.c_int, P]),
     "di_format_impact_lines": (ctypes.c_int, [P, P, P, P, I32, P, I64, P]),
+    "di_format_entry_lines": (ctypes.c_int, [P, P, I64, P, P, P, P, I32, P, I64, P]),
     "di_append_run_lines": (ctypes.c_int, [ctypes.c_char_p, P, P, I32, P, P, P, I32]),
     "di_sparse_create": (ctypes.c_int, [P, I64, P, P, U32, ctypes.c_int, P]),
     "di_sparse_search": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, U32]),
@@ -422,6 +431,65 @@ def segment_order(scores, cu_seg, device=0, stream=0):
     return out[:scores.size]
 
 
+def _check_entries(rc, needed):
+    """check() for the calls that report the entries needed with DI_ERANGE: the DIError
+    carries them as .needed."""
+    if rc == DI_ERANGE:
+        e = DIError(rc, lib().di_last_error().decode("utf-8", "replace"))
+        e.needed = needed
+        raise e
+    check(rc)
+
+
+def pairwise_order(single, pair, cu_terms, cu_pairs, single_pos=None, round3=False, out_cap=None,
+                   device=0, stream=0):
+    """di_pairwise_order: the entries of DeepPairwiseImpact.compute_term_impacts
+    (pairwise_impact.py:98-129) in their order.  single / pair: di_encode_pairwise's
+    arrays (terms sorted by token index, pairs in combination order); single_pos: the
+    position in the document's map of every sorted term (None: the identity).
+    numpy in -> (cu_out int64 [n_docs + 1], first int32, second int32 (-1: a single term),
+    score float32); torch device tensors in (all of them) -> torch device tensors out.
+    first / second index the sorted terms globally.  out_cap: capacity of the entry
+    arrays (default: every pair kept); too small raises DIError DI_ERANGE."""
+    n_docs = len(cu_terms) - 1
+    n = I64(0)
+    flags = DI_F_ROUND3 if round3 else 0
+    if _is_device(single) or _is_device(cu_terms):
+        import torch
+
+        n_terms, n_pairs = int(single.numel()), int(pair.numel())
+        cap = n_terms + n_pairs if out_cap is None else int(out_cap)
+        dev = cu_terms.device
+        cu_out = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        first = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        second = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        score = torch.empty(max(1, cap), dtype=torch.float32, device=dev)
+        flags |= DI_F_DEVICE_PTRS
+    else:
+        single = np.ascontiguousarray(single, np.float32)
+        pair = np.ascontiguousarray(pair, np.float32)
+        cu_terms = np.ascontiguousarray(cu_terms, np.int32)
+        cu_pairs = np.ascontiguousarray(cu_pairs, np.int64)
+        if single_pos is not None:
+            single_pos = np.ascontiguousarray(single_pos, np.int32)
+        n_terms, n_pairs = single.size, pair.size
+        cap = n_terms + n_pairs if out_cap is None else int(out_cap)
+        if single.size == 0:
+            single = np.zeros(1, np.float32)
+        if pair.size == 0:
+            pair = np.zeros(1, np.float32)
+        cu_out = np.zeros(n_docs + 1, np.int64)
+        first = np.zeros(max(1, cap), np.int32)
+        second = np.zeros(max(1, cap), np.int32)
+        score = np.zeros(max(1, cap), np.float32)
+    rc = lib().di_pairwise_order(ptr(single), ptr(pair), ptr(cu_terms), ptr(cu_pairs),
+                                 ptr(single_pos), n_docs, n_terms, n_pairs, ptr(cu_out),
+                                 ptr(first), ptr(second), ptr(score), cap, ctypes.byref(n),
+                                 device, ctypes.c_void_p(stream or 0), flags)
+    _check_entries(rc, n.value)
+    return cu_out, first[:n.value], second[:n.value], score[:n.value]
+
+
 def key_doc(keys, wide=False):
     """Doc of quantized-index merge keys (di_key_doc / di_key_doc_wide); wide: the
     keys of a query of more than DI_SHORT_QUERY_TERMS known terms."""
@@ -474,6 +542,38 @@ def format_impact_lines_packed(blob: bytes, term_off, impacts, cu_terms) -> str:
     tb = ctypes.create_string_buffer(blob, len(blob) + 1)
     check(lib().di_format_impact_lines(tb, ptr(term_off), ptr(imp), ptr(cu), n_docs, out, cap,
                                        ctypes.byref(n)))
+    return out.raw[:n.value].decode("utf-8")
+
+
+def format_entry_lines(blob: bytes, term_off, first, second, score, cu_out, out_cap=None) -> str:
+    """di_format_entry_lines: the impact-TSV lines of di_pairwise_order's entries.  blob /
+    term_off: the batch's terms as in format_impact_lines_packed; entry e is term first[e],
+    or 'term first[e]|term second[e]' when second[e] >= 0, with score[e]; document d holds
+    the entries cu_out[d] .. cu_out[d + 1]."""
+    n_docs = len(cu_out) - 1
+    term_off = np.ascontiguousarray(term_off, np.int64)
+    cu = np.ascontiguousarray(cu_out, np.int64)
+    first = np.ascontiguousarray(first, np.int32)
+    second = np.ascontiguousarray(second, np.int32)
+    score = np.ascontiguousarray(score, np.float32)
+    n_terms, n_ent = len(term_off) - 1, int(cu[-1])
+    if first.size < n_ent or second.size < n_ent or score.size < n_ent:
+        raise ValueError("cu_out names more entries than the arrays hold")
+    if n_ent == 0:
+        first, second, score = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.float32)
+    if out_cap is None:
+        # an entry: at most its two terms, '|', ': ', a float32's repr (<= 24) and ', '
+        # (indices clipped for the estimate only: the library rejects a bad one)
+        lens = np.diff(term_off) if n_terms else np.zeros(1, np.int64)
+        f, s = first[:n_ent].clip(0, max(n_terms - 1, 0)), second[:n_ent]
+        names = int(lens[f].sum()) + int((lens[s.clip(0, max(n_terms - 1, 0))] + 1)[s >= 0].sum())
+        out_cap = names + 28 * n_ent + n_docs + 16
+    out = ctypes.create_string_buffer(max(1, int(out_cap)))
+    n = ctypes.c_int64(0)
+    tb = ctypes.create_string_buffer(blob, len(blob) + 1)
+    check(lib().di_format_entry_lines(tb, ptr(term_off), n_terms, ptr(first), ptr(second),
+                                      ptr(score), ptr(cu), n_docs, out, int(out_cap),
+                                      ctypes.byref(n)))
     return out.raw[:n.value].decode("utf-8")
 
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "di_common.h"
+#include "pair_order.h"
 
 namespace di {
 
@@ -54,6 +55,10 @@ struct di_encoder {
     di::DevBuf pair_w, Mx, uv, cu_sq, cup;
     float pair_w0 = 0.f, pair_b = 0.f;
     const di::PairRun *pair_run = nullptr;
+    // di_encode_pairwise_entries: the unrounded singles and pairs, single_pos, and the
+    // ordering's scratch
+    di::DevBuf ent_single, ent_pair, ent_pos;
+    di::PairOrderWs order;
     di::DevBuf pinfo;  // di_encode_pairs: (n_tokens, max_len, error bits) of the pack
     di::Timer timer;
 };

@@ -293,6 +293,10 @@ void di::ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms)
         e->uv.reserve((size_t)std::max<int64_t>(n_terms, 1) * 8);
         e->cu_sq.reserve((size_t)(n_docs + 1) * 8);
         e->cup.reserve((size_t)(n_docs + 1) * 8);
+        // di_encode_pairwise_entries (the pair scores grow in the call, as Mx)
+        e->ent_single.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
+        e->ent_pos.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
+        e->order.reserve_docs(n_docs);
     }
 }
 
@@ -780,17 +784,23 @@ struct PairCall {
     const int64_t *cu_pairs;
     int64_t n_pairs;
     float *out_pair, *out_attn;
+    // di_encode_pairwise_entries: out / out_pair are device buffers of the workspace even
+    // when the inputs are host arrays; *n_pairs_out receives the batch's pairs
+    bool dev_out = false;
+    int64_t *n_terms_out = nullptr, *n_pairs_out = nullptr;
 };
 
 void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlens, int32_t n_docs,
                  int64_t n_tokens, int32_t max_len, const int32_t *term_tok,
                  const int32_t *cu_terms, int64_t n_terms, float *out, uint32_t flags,
                  const PairCall *pc) {
-    DI_REQUIRE(e && cu_seqlens && out && n_docs >= 0, DI_EINVAL, "bad argument");
+    DI_REQUIRE(e && cu_seqlens && (out || (pc && pc->dev_out)) && n_docs >= 0, DI_EINVAL,
+               "bad argument");
     DeviceScope ds(e->device);
     const bool dev = flags & DI_F_DEVICE_PTRS;
     const bool timing = flags & DI_F_TIMING;
     const bool token_out = !pc && (flags & DI_F_TOKEN_IMPACTS);
+    const bool dev_out = dev || (pc && pc->dev_out);
     int64_t n_pairs = pc ? pc->n_pairs : 0, mx_need = 0;
     hipStream_t s = e->stream;
     if (!dev) {
@@ -839,8 +849,15 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
     DI_REQUIRE(max_len <= e->cfg.max_positions, DI_ERANGE,
                "a document has %d tokens > max_positions %d", max_len,
                e->cfg.max_positions);
+    if (pc && pc->n_terms_out) *pc->n_terms_out = n_terms, *pc->n_pairs_out = n_pairs;
     if (n_docs == 0) return;
     ensure_workspace(e, n_tokens, n_docs, n_terms);
+    float *out_pair = pc ? pc->out_pair : nullptr;
+    if (pc && pc->dev_out) {  // (after ensure_workspace: it may have moved ent_single)
+        e->ent_pair.reserve((size_t)std::max<int64_t>(n_pairs, 1) * 4);
+        out = e->ent_single.as<float>();
+        out_pair = e->ent_pair.as<float>();
+    }
     const int32_t *d_ids =
         (const int32_t *)stage_in(tok_ids, (size_t)n_tokens * 4, dev, e->ids, s);
     const int32_t *d_cu =
@@ -906,7 +923,7 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
             DI_HIP(hipMemcpyAsync(out, e->impact.p, (size_t)n_tokens * 4,
                                   hipMemcpyDeviceToHost, s));
     } else {
-        if (!dev) {
+        if (!dev_out) {
             tmp.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
             d_out = tmp.as<float>();
         }
@@ -917,14 +934,14 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
                                 ((flags & DI_F_ROUND3) ? 1 : 0) | (prune && n_tokens > 0 ? 2 : 0),
                                 d_out, e->err.as<int32_t>(), s);
         }
-        if (!dev && n_terms)
+        if (!dev_out && n_terms)
             DI_HIP(hipMemcpyAsync(out, d_out, (size_t)n_terms * 4, hipMemcpyDeviceToHost,
                                   s));
     }
     DevBuf tmp_pair, tmp_attn;
     if (pc && n_pairs > 0) {
-        float *d_pair = pc->out_pair, *d_attn = pc->out_attn;
-        if (!dev) {
+        float *d_pair = out_pair, *d_attn = pc->out_attn;
+        if (!dev_out) {
             tmp_pair.reserve((size_t)n_pairs * 4);
             d_pair = tmp_pair.as<float>();
             if (pc->out_attn) {
@@ -947,7 +964,7 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
                               (flags & DI_F_ROUND3) ? 1 : 0, d_pair, d_attn,
                               e->err.as<int32_t>(), s);
         }
-        if (!dev) {
+        if (!dev_out) {
             DI_HIP(hipMemcpyAsync(pc->out_pair, d_pair, (size_t)n_pairs * 4,
                                   hipMemcpyDeviceToHost, s));
             if (pc->out_attn)
@@ -1175,6 +1192,44 @@ int di_encode_pairwise(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_
         const PairCall pc{cu_pairs, n_pairs, out_pair, out_pair_attn};
         encode_impl(e, tok_ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
                     n_terms, out_single, flags, &pc);
+    });
+}
+
+int di_encode_pairwise_entries(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlens,
+                               int32_t n_docs, int64_t n_tokens, int32_t max_len,
+                               const int32_t *term_tok, const int32_t *cu_terms, int64_t n_terms,
+                               const int64_t *cu_pairs, int64_t n_pairs,
+                               const int32_t *single_pos, int64_t *out_cu, int32_t *out_first,
+                               int32_t *out_second, float *out_score, int64_t out_cap,
+                               int64_t *n_out, uint32_t flags) {
+    return guard([&] {
+        DI_REQUIRE(e && cu_pairs && out_cu && n_out && out_cap >= 0, DI_EINVAL, "bad argument");
+        DI_REQUIRE(e->has_pair, DI_EINVAL,
+                   "the encoder was created without pairwise_impact_score_encoder");
+        DI_REQUIRE(e->cfg.precision != DI_PREC_BF16, DI_EINVAL,
+                   "pairwise impacts need precision fp32 or bf16x3 (bf16 is not fp32-faithful)");
+        DI_REQUIRE(!(flags & DI_F_TOKEN_IMPACTS), DI_EINVAL, "pairwise: term output only");
+        DeviceScope ds(e->device);
+        const bool dev = flags & DI_F_DEVICE_PTRS;
+        // the forward, unrounded, into ent_single / ent_pair; it waits for the stream and
+        // reports the arrays' errors before anything is ordered
+        PairCall pc{cu_pairs, n_pairs, nullptr, nullptr};
+        pc.dev_out = true;
+        pc.n_terms_out = &n_terms;
+        pc.n_pairs_out = &n_pairs;
+        encode_impl(e, tok_ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
+                    n_terms, nullptr, flags & ~(uint32_t)(DI_F_ROUND3 | DI_F_ASYNC), &pc);
+        hipStream_t s = e->stream;
+        // (encode_impl staged the host offsets into cut / cup; n_docs = 0 stages nothing)
+        const int32_t *d_ct = dev || n_docs == 0 ? cu_terms : e->cut.as<int32_t>();
+        const int64_t *d_cp = dev || n_docs == 0 ? cu_pairs : e->cup.as<int64_t>();
+        const int32_t *d_sp = nullptr;
+        if (single_pos && n_terms > 0)
+            d_sp = (const int32_t *)stage_in(single_pos, (size_t)n_terms * 4, dev, e->ent_pos, s);
+        pairwise_order_run(e->order, &e->timer, flags & DI_F_TIMING, e->ent_single.as<float>(),
+                           e->ent_pair.as<float>(), d_ct, d_cp, d_sp, n_docs, n_terms, n_pairs,
+                           out_cu, out_first, out_second, out_score, out_cap, n_out, dev,
+                           flags & DI_F_ROUND3, s);
     });
 }
 

@@ -52,6 +52,67 @@ extern "C" int di_format_impact_lines(const char *terms, const int64_t *term_off
     });
 }
 
+// The lines of DeepPairwiseImpact's entries (pairwise_impact.py:98-129 names them,
+// indexer.py:62-68 writes them): a term, or 'term1|term2', by index into the batch's term
+// blob.  Formatted on host_threads() threads over ranges of whole documents holding about
+// the same number of entries; the output is the ranges' text in order.
+extern "C" int di_format_entry_lines(const char *terms, const int64_t *term_off, int64_t n_terms,
+                                     const int32_t *first, const int32_t *second,
+                                     const float *score, const int64_t *out_cu, int32_t n_docs,
+                                     char *out, int64_t out_cap, int64_t *out_len) {
+    return guard([&] {
+        DI_REQUIRE(term_off && out_cu && out_len && n_docs >= 0 && n_terms >= 0, DI_EINVAL,
+                   "null argument");
+        const int64_t ne = out_cu[n_docs] - out_cu[0];
+        DI_REQUIRE(ne == 0 || (terms && first && second && score), DI_EINVAL, "null argument");
+        for (int32_t d = 0; d < n_docs; ++d)
+            DI_REQUIRE(out_cu[d + 1] >= out_cu[d], DI_EINVAL, "out_cu not monotone at %d", d);
+        // chunk c: the documents [cut[c], cut[c+1]), cut where the entries reach c / C of all
+        const int C = (int)std::min<int64_t>(std::max(n_docs, 1), 4 * (int64_t)host_threads());
+        std::vector<int32_t> cut((size_t)C + 1, n_docs);
+        cut[0] = 0;
+        for (int c = 1; c < C; ++c) {
+            const int64_t at = out_cu[0] + ne * c / C;
+            const int32_t d = (int32_t)(std::lower_bound(out_cu, out_cu + n_docs, at) - out_cu);
+            cut[(size_t)c] = std::max(cut[(size_t)c - 1], std::min(d, n_docs));
+        }
+        std::vector<std::string> part((size_t)C);
+        parallel_chunks(C, [&](int64_t c, int) {
+            std::string &buf = part[(size_t)c];
+            const int32_t d0 = cut[(size_t)c], d1 = cut[(size_t)c + 1];
+            buf.reserve((size_t)(out_cu[d1] - out_cu[d0]) * 28 + (size_t)(d1 - d0));
+            auto term = [&](int32_t i) {
+                DI_REQUIRE(i >= 0 && i < n_terms, DI_EINVAL, "term index %d outside [0, %lld)", i,
+                           (long long)n_terms);
+                buf.append(terms + term_off[i], (size_t)(term_off[i + 1] - term_off[i]));
+            };
+            for (int32_t d = d0; d < d1; ++d) {
+                for (int64_t e = out_cu[d]; e < out_cu[d + 1]; ++e) {
+                    if (e > out_cu[d]) buf += ", ";
+                    term(first[e]);
+                    if (second[e] >= 0) {
+                        buf += '|';
+                        term(second[e]);
+                    }
+                    buf += ": ";
+                    py::repr_double((double)score[e], buf);
+                }
+                buf += '\n';
+            }
+        });
+        std::vector<int64_t> off((size_t)C + 1, 0);
+        for (int c = 0; c < C; ++c)
+            off[(size_t)c + 1] = off[(size_t)c] + (int64_t)part[(size_t)c].size();
+        *out_len = off[(size_t)C];
+        DI_REQUIRE(out && off[(size_t)C] <= out_cap, DI_ERANGE,
+                   "output buffer too small: %lld bytes needed", (long long)off[(size_t)C]);
+        parallel_for(C, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t c = lo; c < hi; ++c)
+                std::memcpy(out + off[(size_t)c], part[(size_t)c].data(), part[(size_t)c].size());
+        });
+    });
+}
+
 // run-file lines (reference src/utils/datasets.py RunFile.writelines, :305-324):
 // f"{qid}\t{pid}\t{rank}\t{score}\n" for rank = 1.. over each query's (pid, score)
 // list, queries in order, appended to the file.  Integer pids and scores (the quantized

@@ -220,6 +220,49 @@ class DeviceEncoder:
         out = (single[:n_terms], pair[:n_pairs], cu_pairs)
         return out + (attn[:n_pairs],) if attentions else out
 
+    def encode_pairwise_entries(self, ids, cu_seqlens, term_tok, cu_terms, single_pos=None,
+                                round3=False, timing=False, out_cap=None):
+        """di_encode_pairwise_entries: encode_pairwise followed by the device ordering of
+        DeepPairwiseImpact.compute_term_impacts (pairwise_impact.py:98-129); the pair
+        scores stay on the device.  term_tok strictly ascending inside each document;
+        single_pos: the position in the document's map of every sorted term (None: the
+        identity).  Host arrays in -> (cu_out int64 [n_docs + 1], first int32, second
+        int32 (-1: a single term), score float32): entry e of document d (cu_out[d] <= e <
+        cu_out[d + 1]) is the sorted term first[e] (a global index), or the pair (first[e],
+        second[e]).  out_cap: capacity of the entry arrays (default: every pair kept)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, np.int32)
+        tt = np.ascontiguousarray(term_tok, np.int32)
+        ct = np.ascontiguousarray(cu_terms, np.int32)
+        n_docs = len(cu) - 1
+        T = np.diff(ct.astype(np.int64))
+        cu_pairs = np.zeros(n_docs + 1, np.int64)
+        cu_pairs[1:] = np.cumsum(T * (T - 1) // 2)
+        n_terms, n_pairs = int(ct[-1]), max(int(cu_pairs[-1]), 0)
+        if single_pos is not None:
+            single_pos = np.ascontiguousarray(single_pos, np.int32)
+            if single_pos.size != n_terms:
+                raise ValueError("single_pos: one position per term")
+            if n_terms == 0:
+                single_pos = None
+        cap = n_terms + n_pairs if out_cap is None else int(out_cap)
+        cu_out = np.zeros(n_docs + 1, np.int64)
+        # (untouched pages cost nothing: the library writes the entries there are)
+        first, second = np.empty(max(1, cap), np.int32), np.empty(max(1, cap), np.int32)
+        score = np.empty(max(1, cap), np.float32)
+        flags = (DI_F_ROUND3 if round3 else 0) | (_lib.DI_F_TIMING if timing else 0)
+        if tt.size == 0:
+            tt = np.zeros(1, np.int32)
+        if ids.size == 0:
+            ids = np.zeros(1, np.int32)
+        n = ctypes.c_int64(0)
+        rc = lib().di_encode_pairwise_entries(
+            self._h, ptr(ids), ptr(cu), n_docs, 0, 0, ptr(tt), ptr(ct), 0, ptr(cu_pairs), 0,
+            ptr(single_pos), ptr(cu_out), ptr(first), ptr(second), ptr(score), cap,
+            ctypes.byref(n), flags)
+        _lib._check_entries(rc, n.value)
+        return cu_out, first[:n.value], second[:n.value], score[:n.value]
+
     def encode_device(self, ids, cu_seqlens, n_docs, n_tokens, max_len, term_tok, cu_terms,
                       n_terms, out, flags=_lib.DI_F_DEVICE_PTRS):
         check(lib().di_encode(self._h, ptr(ids), ptr(cu_seqlens), n_docs, n_tokens, max_len,

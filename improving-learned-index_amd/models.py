@@ -711,8 +711,17 @@ class DeepPairwiseImpact(DeepImpact):
         return [list(zip(names[cu_out[d]:cu_out[d + 1]], score[cu_out[d]:cu_out[d + 1]]))
                 for d in range(len(maps))]
 
+    @staticmethod
+    def host_order() -> bool:
+        """DI_PAIRWISE_HOST_ORDER=1: order and name the entries on the host
+        (pairwise_entries over encode_pairwise's arrays) -- the second answer of the tests
+        and of tools/pairwise_e2e.py's A/B; default: the device order
+        (di_encode_pairwise_entries) and the native entry formatter."""
+        return os.environ.get("DI_PAIRWISE_HOST_ORDER") == "1"
+
     def _encode_entries(self, ids, cu, terms, tt, ct, round3_):
-        """Device call on a packed batch -> (names, scores, cu_out) of its lines."""
+        """Host path.  Device call on a packed batch -> (names, scores, cu_out) of its
+        lines, ordered and named on the host."""
         tt, ct = np.asarray(tt, np.int32), np.asarray(ct, np.int32)
         n_terms = int(ct[-1])
         tdoc = np.repeat(np.arange(len(ct) - 1), np.diff(ct))
@@ -723,14 +732,44 @@ class DeepPairwiseImpact(DeepImpact):
         names, score, cu_out = _pairwise_named(terms, tt, ct, single, pair, cu_pairs)
         return names, (round3(score) if round3_ else score), cu_out
 
+    def _encode_entries_device(self, ids, cu, tt, ct, round3_):
+        """Device path.  A packed batch -> (cu_out, first, second, score): the entries in
+        their order (di_encode_pairwise_entries), first / second global term indices in
+        map order, second -1 for a single term.  Only the entries reach the host."""
+        tt, ct = np.asarray(tt, np.int32), np.asarray(ct, np.int32)
+        n_terms = int(ct[-1])
+        T = np.diff(ct)
+        asc = np.ones(n_terms, bool)  # ascending from the term before, or a document's first
+        asc[1:] = tt[1:n_terms] > tt[:n_terms - 1]
+        asc[ct[:-1][ct[:-1] < n_terms]] = True
+        if asc.all():  # first-occurrence maps: map order is token order
+            return self.encoder.encode_pairwise_entries(ids, cu, tt[:n_terms], ct, None,
+                                                        round3=round3_)
+        tdoc = np.repeat(np.arange(len(ct) - 1), T)
+        by_tok = np.lexsort((tt[:n_terms], tdoc))
+        pos = (by_tok - ct[tdoc]).astype(np.int32)
+        cu_out, first, second, score = self.encoder.encode_pairwise_entries(
+            ids, cu, tt[:n_terms][by_tok], ct, pos, round3=round3_)
+        by32 = by_tok.astype(np.int32)
+        return cu_out, by32[first], np.where(second >= 0, by32[np.maximum(second, 0)],
+                                              np.int32(-1)).astype(np.int32), score
+
     def encode_packed_terms(self, packed, round3=False):
         ids, cu, terms, tt, ct = packed
-        names, score, cu_out = self._encode_entries(ids, cu, terms, tt, ct, round3)
+        if self.host_order():
+            names, score, cu_out = self._encode_entries(ids, cu, terms, tt, ct, round3)
+        else:
+            cu_out, first, second, score = self._encode_entries_device(ids, cu, tt, ct, round3)
+            names = [terms[f] if s < 0 else f"{terms[f]}|{terms[s]}"
+                     for f, s in zip(first.tolist(), second.tolist())]
         return [list(zip(names[cu_out[d]:cu_out[d + 1]], score[cu_out[d]:cu_out[d + 1]]))
                 for d in range(len(ct) - 1)]
 
     def encode_packed_impacts(self, packed):
         ids, cu, blob, term_off, tt, ct = packed
+        if not self.host_order():
+            cu_out, first, second, score = self._encode_entries_device(ids, cu, tt, ct, True)
+            return lambda: _lib.format_entry_lines(blob, term_off, first, second, score, cu_out)
         terms = [blob[term_off[i]:term_off[i + 1]].decode("utf-8")
                  for i in range(len(term_off) - 1)]
         names, score, cu_out = self._encode_entries(ids, cu, terms, tt, ct, True)

@@ -312,6 +312,57 @@ int di_encode_pairwise(di_encoder *enc, const int32_t *tok_ids, const int32_t *c
                        const int32_t *term_tok, const int32_t *cu_terms, int64_t n_terms,
                        const int64_t *cu_pairs, int64_t n_pairs, float *out_single,
                        float *out_pair, float *out_pair_attn /* may be NULL */, uint32_t flags);
+
+/* Entries of one LDS sort of di_pairwise_order (128 KiB of 64-bit keys): a document of up
+ * to this many entries is ordered by one workgroup, a longer one in runs of this many
+ * that merge passes combine. */
+#define DI_PAIR_ORDER_LDS_KEYS 16384
+/* Terms per document of di_pairwise_order: a key holds the entry's position in 21 bits
+ * and a term's rank in 11 (T (T + 1) / 2 < 2^21).  di_encode_pairwise's own limit of 1232
+ * tokens is below it. */
+#define DI_PAIR_ORDER_MAX_TERMS 2047
+
+/* Replaces the ordering of DeepPairwiseImpact.compute_term_impacts
+ * (src/deep_impact/models/pairwise_impact.py:98-129) for a batch, on the device: per
+ * document the entries are its T terms and the pairs whose score does not round to 0.000
+ * (fl32(rint(fl32(x * 1000)) / 1000) != 0, the round(impact, 3) of
+ * src/deep_impact/indexing/indexer.py:62-68), sorted by raw score descending (-0.0 equals
+ * +0.0), equal scores by position: a term's position is its place in the document's map,
+ * pair j's is T + j.  NaN scores are outside the contract.
+ * single[n_terms], pair[n_pairs], cu_terms[n_docs+1] (int32), cu_pairs[n_docs+1] (int64):
+ * di_encode_pairwise's outputs and offsets -- the terms sorted by token index, the pairs
+ * in combination order -- checked as that call checks them (DI_EINVAL; n_terms and
+ * n_pairs are required with DI_F_DEVICE_PTRS and recomputed otherwise).
+ * single_pos[n_terms] (may be NULL = identity): the position in the document's map of its
+ * r-th sorted term (the identity for first-occurrence maps; a permutation for bert_legacy
+ * maps); a value outside [0, T) is DI_EINVAL.
+ * out_cu[n_docs+1]: offsets of the documents' entries.  Entry e: out_first[e] =
+ * cu_terms[d] + r, the global index of a sorted term, out_second[e] = -1 for a term, or the
+ * two terms of a pair (first < second); out_score[e] its raw score, or the rounded one
+ * with DI_F_ROUND3 (the order always uses the raw score).  *n_out (host) = the entries.
+ * If they exceed out_cap the call writes out_cu and *n_out, no entry, and returns
+ * DI_ERANGE.  Documents of up to DI_PAIR_ORDER_MAX_TERMS terms (DI_ERANGE for host
+ * pointers, DI_EINVAL from the device check).  Runs on hip_stream and waits for it. */
+int di_pairwise_order(const float *single, const float *pair, const int32_t *cu_terms,
+                      const int64_t *cu_pairs, const int32_t *single_pos /* may be NULL */,
+                      int32_t n_docs, int64_t n_terms, int64_t n_pairs, int64_t *out_cu,
+                      int32_t *out_first, int32_t *out_second, float *out_score,
+                      int64_t out_cap, int64_t *n_out, int device, void *hip_stream,
+                      uint32_t flags);
+
+/* di_encode_pairwise followed by di_pairwise_order on the encoder's stream: the forward
+ * runs unrounded into the encoder's workspace, the entries are ordered there, and only
+ * out_cu and the *n_out entries are copied out -- the pair scores never reach the host.
+ * tok_ids .. n_pairs: as di_encode_pairwise; single_pos, out_*: as di_pairwise_order
+ * (DI_F_ROUND3 rounds out_score only).  Always synchronous at return.  DI_F_TIMING adds
+ * "pair_count", "pair_order" and "pair_merge" to di_encode_pairwise's names. */
+int di_encode_pairwise_entries(di_encoder *enc, const int32_t *tok_ids,
+                               const int32_t *cu_seqlens, int32_t n_docs, int64_t n_tokens,
+                               int32_t max_len, const int32_t *term_tok, const int32_t *cu_terms,
+                               int64_t n_terms, const int64_t *cu_pairs, int64_t n_pairs,
+                               const int32_t *single_pos /* may be NULL */, int64_t *out_cu,
+                               int32_t *out_first, int32_t *out_second, float *out_score,
+                               int64_t out_cap, int64_t *n_out, uint32_t flags);
 int di_encoder_reserve(di_encoder *enc, int64_t max_tokens, int32_t max_docs, int64_t max_terms);
 int di_encoder_set_stream(di_encoder *enc, void *hip_stream);
 int di_encoder_sync(di_encoder *enc);
@@ -411,6 +462,20 @@ int di_quantize_file(const char *input_path, const char *output_path, double max
 int di_format_impact_lines(const char *terms, const int64_t *term_off, const float *impacts,
                            const int64_t *cu_doc_terms, int32_t n_docs, char *out,
                            int64_t out_cap, int64_t *out_len);
+
+/* The same lines (indexer.py:62-68) for the entries of di_pairwise_order, whose names
+ * DeepPairwiseImpact.compute_term_impacts builds (pairwise_impact.py:98-129): entry e of
+ * document d (out_cu[d] <= e < out_cu[d+1]) is written as term[first[e]], or
+ * term[first[e]] '|' term[second[e]] when second[e] >= 0, then ": " and the repr of the
+ * float64 value of score[e]; entries joined by ", ", every document ended by '\n' (a
+ * document without entries is "\n").  terms / term_off[n_terms+1]: the batch's terms as
+ * in di_format_impact_lines; first / second index them (an index outside [0, n_terms) is
+ * DI_EINVAL).  Byte-identical to di_format_impact_lines over the joined names; the same
+ * DI_ERANGE contract.  Formatted on DI_HOST_THREADS threads over ranges of documents. */
+int di_format_entry_lines(const char *terms, const int64_t *term_off, int64_t n_terms,
+                          const int32_t *first, const int32_t *second, const float *score,
+                          const int64_t *out_cu, int32_t n_docs, char *out, int64_t out_cap,
+                          int64_t *out_len);
 
 /* Replaces RunFile.writelines (src/utils/datasets.py:305-324) over a batch: appends
  * to `path`, for each query q (its id qids[qid_off[q] .. qid_off[q+1]), UTF-8) and rank
