@@ -25,6 +25,7 @@ DI_MAX_QUERY_TERMS = 4096
 DI_MAX_TOPK = 4096
 DI_PAIR_ORDER_LDS_KEYS = 16384  # entries one workgroup orders in LDS (include/deepimpact.h)
 DI_PAIR_ORDER_MAX_TERMS = 2047
+DI_TERM_STORE_MAX_TERMS = 2048  # pairs of one passage of a TermStore (include/deepimpact.h)
 DI_F_ROUND3 = 0x10
 DI_ERANGE = -4
 
@@ -114,6 +115,13 @@ SIGNATURES = {
                                      ctypes.c_int, P, U32]),
     "di_encode_pairs": (ctypes.c_int, [P, P, P, I32, P, P, I32, P, P, I32, P, P, U32]),
     "di_segment_order": (ctypes.c_int, [P, P, I32, P, ctypes.c_int, P, U32]),
+    "di_term_store_create": (ctypes.c_int, [ctypes.c_int, P]),
+    "di_term_store_reserve": (ctypes.c_int, [P, I64, I64]),
+    "di_term_store_append": (ctypes.c_int, [P, P, P, P, I32, P, P, U32]),
+    "di_term_store_info": (ctypes.c_int, [P, P, P, P]),
+    "di_term_store_score": (ctypes.c_int, [P, P, P, I32, P, P, P, P, P, U32]),
+    "di_term_store_timing": (ctypes.c_int, [P, ctypes.c_char_p, P, ctypes.c_int]),
+    "di_term_store_destroy": (ctypes.c_int, [P]),
     "di_quantize": (ctypes.c_int, [P, I64, ctypes.c_double, I32, P, P, ctypes.c_int, P, U32]),
     "di_quantize_file": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, I32,
                                         ctypes.c_int, P]),
@@ -344,6 +352,101 @@ class DeviceIndex:
     def close(self):
         if self._h:
             lib().di_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TermStore:
+    """Device-resident (term id, impact) lists per passage (di_term_store_*): the
+    re-ranker's per-pid cache (reranker.py:39,48-53) on the GPU."""
+
+    def __init__(self, device=0, n_docs=0, n_terms=0):
+        h = ctypes.c_void_p()
+        check(lib().di_term_store_create(device, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+        if n_docs or n_terms:
+            self.reserve(n_docs, n_terms)
+
+    def reserve(self, n_docs, n_terms):
+        check(lib().di_term_store_reserve(self._h, int(n_docs), int(n_terms)))
+
+    def append(self, term_ids, impacts, cu_terms, stream=0, timing=False):
+        """Appends len(cu_terms) - 1 passages; passage d holds (term_ids[i], impacts[i]) for
+        i in [cu_terms[d], cu_terms[d + 1]).  Host numpy arrays, or torch device tensors
+        (all three; term ids as int32 bit patterns).  Returns the store index of the first
+        appended passage."""
+        n_docs = len(cu_terms) - 1
+        flags = DI_F_TIMING if timing else 0
+        if _is_device(cu_terms):
+            flags |= DI_F_DEVICE_PTRS
+        else:
+            term_ids = np.ascontiguousarray(term_ids, np.uint32)
+            impacts = np.ascontiguousarray(impacts, np.float32)
+            cu_terms = np.ascontiguousarray(cu_terms, np.int32)
+            if term_ids.size != impacts.size or (n_docs > 0 and term_ids.size < cu_terms[-1]):
+                raise ValueError("term_ids and impacts: one entry per pair of cu_terms")
+            if term_ids.size == 0:
+                term_ids, impacts = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        first = I64(0)
+        check(lib().di_term_store_append(self._h, ptr(term_ids), ptr(impacts), ptr(cu_terms),
+                                         n_docs, ctypes.byref(first),
+                                         ctypes.c_void_p(stream or 0), flags))
+        return first.value
+
+    def score(self, q_terms, cu_q, cand_doc, cu_cand, stream=0, timing=False):
+        """di_term_store_score: for every candidate cand_doc[c] of every query, the float32
+        sum of the impacts of the query's terms the passage holds, added in the query's
+        order, and the number of terms that matched.  Host numpy arrays in -> (scores
+        float32, match int32) numpy; torch device tensors in (all four) -> torch device
+        tensors."""
+        n_q = len(cu_q) - 1
+        flags = DI_F_TIMING if timing else 0
+        if _is_device(cand_doc):
+            import torch
+
+            n_c = int(cand_doc.numel())
+            scores = torch.empty(max(1, n_c), dtype=torch.float32, device=cand_doc.device)
+            match = torch.empty(max(1, n_c), dtype=torch.int32, device=cand_doc.device)
+            flags |= DI_F_DEVICE_PTRS
+        else:
+            q_terms = np.ascontiguousarray(q_terms, np.uint32)
+            cu_q = np.ascontiguousarray(cu_q, np.int32)
+            cand_doc = np.ascontiguousarray(cand_doc, np.int32)
+            cu_cand = np.ascontiguousarray(cu_cand, np.int32)
+            n_c = cand_doc.size
+            if n_q > 0 and (cu_cand[-1] > n_c or cu_q[-1] > q_terms.size):
+                raise ValueError("cu_cand / cu_q name more entries than the arrays hold")
+            if q_terms.size == 0:
+                q_terms = np.zeros(1, np.uint32)
+            if n_c == 0:
+                cand_doc = np.zeros(1, np.int32)
+            scores = np.zeros(max(1, n_c), np.float32)
+            match = np.zeros(max(1, n_c), np.int32)
+        check(lib().di_term_store_score(self._h, ptr(q_terms), ptr(cu_q), n_q, ptr(cand_doc),
+                                        ptr(cu_cand), ptr(scores), ptr(match),
+                                        ctypes.c_void_p(stream or 0), flags))
+        return scores[:n_c], match[:n_c]
+
+    def info(self):
+        nd, nt, nb = I64(), I64(), I64()
+        check(lib().di_term_store_info(self._h, ctypes.byref(nd), ctypes.byref(nt),
+                                       ctypes.byref(nb)))
+        return {"n_docs": nd.value, "n_terms": nt.value, "device_bytes": nb.value}
+
+    def timing(self, name, reset=False):
+        t = di_timing()
+        check(lib().di_term_store_timing(self._h, name.encode(), ctypes.byref(t), int(reset)))
+        return t.ms, t.launches
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().di_term_store_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -433,6 +433,62 @@ int di_segment_order(const float *scores, const int32_t *cu_seg, int32_t n_seg, 
                      int device, void *hip_stream, uint32_t flags);
 
 /* ======================================================================
+ * Re-ranking with the impact model: a device store of term impacts    (F3)
+ * ====================================================================== */
+typedef struct di_term_store di_term_store;
+
+/* (term id, impact) pairs of one passage of the store; a longer passage is DI_ERANGE. */
+#define DI_TERM_STORE_MAX_TERMS 2048
+
+/* Replaces ReRanker.__init__'s per-pid cache (src/deep_impact/evaluation/reranker.py:13-41):
+ * an empty store on `device`.  A handle is not thread-safe.  Every call below runs on the
+ * hip_stream it is given and waits for it before returning (the device error word is read
+ * back): DI_F_ASYNC is accepted and has no effect. */
+int di_term_store_create(int device, di_term_store **out);
+/* Capacity for n_docs passages and n_terms pairs in all (never shrinks). */
+int di_term_store_reserve(di_term_store *ts, int64_t n_docs, int64_t n_terms);
+
+/* Replaces ReRanker.save (reranker.py:48-50): appends n_docs passages; passage d holds the
+ * pairs (term_ids[i], impacts[i]), i in [cu_terms[d], cu_terms[d+1]).  Term ids are whatever
+ * the caller assigns to distinct term strings.  *first_doc (host) receives the store index
+ * of the first appended passage; the others follow it.  On the device each passage's pairs
+ * are kept sorted by term id.  With DI_F_DEVICE_PTRS the three arrays are device pointers
+ * (e.g. impacts = the buffer di_encode wrote with DI_F_DEVICE_PTRS: the impacts never visit
+ * the host); ordering between the stream that produced them and hip_stream is the
+ * caller's business.  An empty passage is legal.  Appending past the reservation grows the
+ * buffers; earlier passages keep their indices and contents.
+ * Errors, after which nothing is appended and the store is as before: a passage of more
+ * than DI_TERM_STORE_MAX_TERMS pairs, DI_ERANGE; cu_terms not starting at 0 or decreasing,
+ * DI_EINVAL; the same term id twice in one passage, DI_EINVAL (found on the device after
+ * the sort and reported through an error word, as di_encode reports a bad term index).
+ * DI_F_TIMING: "ts_sort". */
+int di_term_store_append(di_term_store *ts, const uint32_t *term_ids, const float *impacts,
+                         const int32_t *cu_terms, int32_t n_docs, int64_t *first_doc,
+                         void *hip_stream, uint32_t flags);
+/* Passages and pairs held, and the bytes of the two device buffers that hold them. */
+int di_term_store_info(const di_term_store *ts, int64_t *n_docs, int64_t *n_terms,
+                       int64_t *device_bytes);
+
+/* Replaces ReRanker.score (reranker.py:52-53) for every candidate of n_q queries:
+ * q_terms CSR by cu_q[n_q+1] (the query's terms in the iteration order of its Python
+ * set), candidates cand_doc[c] (store indices), c in [cu_cand[q], cu_cand[q+1]).  For
+ * candidate c of query q: acc = +0.0f; for j in [cu_q[q], cu_q[q+1]) in that order, if
+ * passage cand_doc[c] holds q_terms[j], acc = acc + impact -- plain f32 round-to-nearest
+ * adds in the query's order, a term that occurs twice adds twice.  out_score[c] = acc,
+ * out_match[c] = the number of adds: the reference's sum() is the int 0 (written "0")
+ * when nothing matched and a float (written "0.0" even if it is zero) otherwise.
+ * Queries of up to DI_MAX_QUERY_TERMS terms (DI_ERANGE).  A candidate index outside the
+ * store: DI_EINVAL through the error word; its score and match count are written 0 and
+ * nothing is read out of bounds.  Host pointers, or device pointers with DI_F_DEVICE_PTRS
+ * (then the limits are checked on the device).  DI_F_TIMING: "ts_score". */
+int di_term_store_score(di_term_store *ts, const uint32_t *q_terms, const int32_t *cu_q,
+                        int32_t n_q, const int32_t *cand_doc, const int32_t *cu_cand,
+                        float *out_score, int32_t *out_match, void *hip_stream, uint32_t flags);
+/* HIP-event time of "ts_sort" / "ts_score" over the DI_F_TIMING calls since the last reset. */
+int di_term_store_timing(di_term_store *ts, const char *name, di_timing *out, int reset);
+int di_term_store_destroy(di_term_store *ts);
+
+/* ======================================================================
  * 8-bit quantizer                                          (A10)
  * ====================================================================== */
 /* Replaces quantize_file's arithmetic (src/deep_impact/indexing/quantize.py:13-47):
