@@ -28,6 +28,9 @@ DI_PAIR_ORDER_MAX_TERMS = 2047
 DI_TERM_STORE_MAX_TERMS = 2048  # pairs of one passage of a TermStore (include/deepimpact.h)
 DI_F_ROUND3 = 0x10
 DI_ERANGE = -4
+DI_EINVAL = -1
+DI_MAX_SPARSE_DOCS = 16777215  # documents of a float index (include/deepimpact.h)
+SPARSE_BLOCK_DOCS = 16384  # documents of one block of the float index's layout
 
 _ERRNAMES = {-1: "DI_EINVAL", -2: "DI_ENOMEM", -3: "DI_EHIP", -4: "DI_ERANGE",
              -5: "DI_ENODEV", -6: "DI_EIO", -7: "DI_EFORMAT"}
@@ -134,6 +137,13 @@ SIGNATURES = {
     "di_sparse_info": (ctypes.c_int, [P, P, P, P, P]),
     "di_sparse_timing": (ctypes.c_int, [P, ctypes.c_char_p, P, ctypes.c_int]),
     "di_sparse_destroy": (ctypes.c_int, [P]),
+    "di_sparse_builder_create": (ctypes.c_int, [ctypes.c_int, P]),
+    "di_sparse_builder_reserve": (ctypes.c_int, [P, I64, I64]),
+    "di_sparse_builder_append": (ctypes.c_int, [P, P, P, P, I32, P, P, U32]),
+    "di_sparse_builder_info": (ctypes.c_int, [P, P, P]),
+    "di_sparse_builder_finish": (ctypes.c_int, [P, I64, P, U32, P]),
+    "di_sparse_builder_destroy": (ctypes.c_int, [P]),
+    "di_sparse_export": (ctypes.c_int, [P, P, P, P, P]),
     "di_synth_postings": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P, P, I64,
                                          P, P]),
     "di_synth_postings_skewed": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P,
@@ -718,6 +728,39 @@ class DeviceSparseIndex:
                                      n_docs, device, ctypes.byref(h)))
         self._h = h
 
+    @classmethod
+    def _from_handle(cls, h):
+        self = cls.__new__(cls)
+        self._h = h
+        return self
+
+    def info(self):
+        nt, npost, nd, nb = I64(), I64(), U32(), I32()
+        check(lib().di_sparse_info(self._h, ctypes.byref(nt), ctypes.byref(npost),
+                                   ctypes.byref(nd), ctypes.byref(nb)))
+        return {"n_terms": nt.value, "n_postings": npost.value, "n_docs": nd.value,
+                "n_blocks": nb.value}
+
+    def export(self):
+        """di_sparse_export: the device layout on the host, (term_start int64 [n_terms],
+        blk_off uint32 [n_terms, n_blocks + 1], pdoc uint16 [n_postings] (doc % 16384),
+        pimp float32 [n_postings]).  Term t's postings of block b are
+        [term_start[t] + blk_off[t, b], term_start[t] + blk_off[t, b + 1]), docs ascending;
+        blk_off[t, n_blocks] is its posting count."""
+        i = self.info()
+        term_start = np.zeros(i["n_terms"], np.int64)
+        blk_off = np.zeros((i["n_terms"], i["n_blocks"] + 1), np.uint32)
+        pdoc = np.zeros(i["n_postings"], np.uint16)
+        pimp = np.zeros(i["n_postings"], np.float32)
+        check(lib().di_sparse_export(self._h, ptr(term_start), ptr(blk_off), ptr(pdoc),
+                                     ptr(pimp)))
+        return term_start, blk_off, pdoc, pimp
+
+    def timing(self, name, reset=False):
+        t = di_timing()
+        check(lib().di_sparse_timing(self._h, name.encode(), ctypes.byref(t), int(reset)))
+        return t.ms, t.launches
+
     def search_csr(self, q_terms, cu_q, k, with_keys=False, accumulation="f32"):
         """accumulation "f32" (numpy >= 2) or "f64" (the reference's pinned numpy 1.25:
         f64 scores; no keys)."""
@@ -753,6 +796,70 @@ class DeviceSparseIndex:
     def close(self):
         if getattr(self, "_h", None):
             lib().di_sparse_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SparseBuilder:
+    """Device builder of the float index (di_sparse_builder_*): documents appended as
+    (term id, impact) pairs -- host arrays, or the device buffers of an encode step --
+    and assembled into a DeviceSparseIndex on the GPU."""
+
+    def __init__(self, device=0, n_docs=0, n_pairs=0):
+        h = ctypes.c_void_p()
+        check(lib().di_sparse_builder_create(device, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+        if n_docs or n_pairs:
+            self.reserve(n_docs, n_pairs)
+
+    def reserve(self, n_docs, n_pairs):
+        check(lib().di_sparse_builder_reserve(self._h, int(n_docs), int(n_pairs)))
+
+    def append(self, term_ids, impacts, cu_terms, stream=0, timing=False):
+        """Appends len(cu_terms) - 1 documents; document d holds (term_ids[i], impacts[i])
+        for i in [cu_terms[d], cu_terms[d + 1]); pairs whose impact is not > 0 are dropped.
+        Host numpy arrays, or torch device tensors (all three; term ids as int32 bit
+        patterns).  Returns the corpus position of the first appended document."""
+        n_docs = len(cu_terms) - 1
+        flags = DI_F_TIMING if timing else 0
+        if _is_device(cu_terms):
+            flags |= DI_F_DEVICE_PTRS
+        else:
+            term_ids = np.ascontiguousarray(term_ids, np.uint32)
+            impacts = np.ascontiguousarray(impacts, np.float32)
+            cu_terms = np.ascontiguousarray(cu_terms, np.int32)
+            if term_ids.size != impacts.size or (n_docs > 0 and term_ids.size < cu_terms[-1]):
+                raise ValueError("term_ids and impacts: one entry per pair of cu_terms")
+            if term_ids.size == 0:
+                term_ids, impacts = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        first = I64(0)
+        check(lib().di_sparse_builder_append(self._h, ptr(term_ids), ptr(impacts),
+                                             ptr(cu_terms), n_docs, ctypes.byref(first),
+                                             ctypes.c_void_p(stream or 0), flags))
+        return first.value
+
+    def info(self):
+        nd, npairs = I64(), I64()
+        check(lib().di_sparse_builder_info(self._h, ctypes.byref(nd), ctypes.byref(npairs)))
+        return {"n_docs": nd.value, "n_pairs": npairs.value}
+
+    def finish(self, n_terms, stream=0, timing=False) -> DeviceSparseIndex:
+        """The index of everything appended over terms 0 .. n_terms - 1 (the builder stays
+        as it is).  A term id >= n_terms, or a term twice in one document: DI_EINVAL."""
+        h = ctypes.c_void_p()
+        check(lib().di_sparse_builder_finish(self._h, int(n_terms), ctypes.c_void_p(stream or 0),
+                                             DI_F_TIMING if timing else 0, ctypes.byref(h)))
+        return DeviceSparseIndex._from_handle(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().di_sparse_builder_destroy(self._h)
             self._h = None
 
     def __del__(self):

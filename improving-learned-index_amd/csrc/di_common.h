@@ -281,4 +281,22 @@ inline const void *stage_in(const void *src, size_t bytes, bool device_ptrs, Dev
     return buf.p;
 }
 
+// `buf` with room for `need` bytes, its first `used` bytes kept.  Waits for s.
+inline void grow_keep(DevBuf &buf, size_t need, size_t used, hipStream_t s) {
+    if (need <= buf.bytes && buf.p) return;
+    const size_t bytes = std::max(need, 2 * buf.bytes);
+    void *p = nullptr;
+    DI_HIP(hipMalloc(&p, bytes));
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(p, buf.p, used, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        DI_HIP(e);
+    }
+    if (buf.p) (void)hipFree(buf.p);
+    buf.p = p;
+    buf.bytes = bytes;
+}
+
 }  // namespace di

@@ -171,24 +171,6 @@ struct DeviceScope {
     }
 };
 
-// `buf` with room for `need` bytes, its first `used` bytes kept.  Waits for s.
-void grow_keep(DevBuf &buf, size_t need, size_t used, hipStream_t s) {
-    if (need <= buf.bytes && buf.p) return;
-    const size_t bytes = std::max(need, 2 * buf.bytes);
-    void *p = nullptr;
-    DI_HIP(hipMalloc(&p, bytes));
-    hipError_t e = hipSuccess;
-    if (used) e = hipMemcpyAsync(p, buf.p, used, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        DI_HIP(e);
-    }
-    if (buf.p) (void)hipFree(buf.p);
-    buf.p = p;
-    buf.bytes = bytes;
-}
-
 int32_t read_i32(const int32_t *d_p, hipStream_t s) {
     int32_t v = 0;
     DI_HIP(hipMemcpyAsync(&v, d_p, 4, hipMemcpyDeviceToHost, s));

@@ -28,12 +28,11 @@
 #include <memory>
 #include <vector>
 
-#include "di_common.h"
+#include "sparse_common.h"
 #include "topk_common.h"
 
 namespace di {
 
-constexpr int SP_DOCS = 16384;
 constexpr int SP_THREADS = 1024;
 constexpr int SP_WAVES = SP_THREADS / 64;
 constexpr int SP_PER_THREAD = SP_DOCS / SP_THREADS;  // 16
@@ -411,35 +410,25 @@ void launch_merge(const uint64_t *keys, const int32_t *counts, int n_q, int n_li
                   const int32_t *cu_q);
 void enable_big_lds();
 
+void sparse_init(di_sparse &sp, int device) {
+    sp.device = device;
+    DI_HIP(hipStreamCreateWithFlags(&sp.stream, hipStreamNonBlocking));
+    sp.own_stream = true;
+    enable_big_lds();
+    DI_HIP(hipFuncSetAttribute((const void *)sparse_score_kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sizeof(SparseShared)));
+    DI_HIP(hipFuncSetAttribute((const void *)sparse_score64_kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sizeof(Sparse64Shared)));
+    DI_HIP(hipFuncSetAttribute((const void *)sparse_merge64_kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sizeof(Merge64Shared)));
+}
+
 }  // namespace di
 
 using namespace di;
-
-struct di_sparse {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int64_t n_terms = 0, n_post = 0;
-    uint32_t n_docs = 0;
-    int nb = 0;
-    DevBuf pdoc, pimp, term_start, blk_off;
-    DevBuf ws_q, ws_cu, ws_ck, ws_cn, ws_doc, ws_score, ws_n, ws_key;
-    Timer timer;
-};
-
-namespace {
-struct DevScope {
-    int prev = -1;
-    explicit DevScope(int d) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != d) DI_HIP(hipSetDevice(d));
-    }
-    ~DevScope() {
-        int c;
-        if (hipGetDevice(&c) == hipSuccess && c != prev) (void)hipSetDevice(prev);
-    }
-};
-}  // namespace
 
 extern "C" {
 
@@ -454,19 +443,7 @@ int di_sparse_create(const int64_t *term_off, int64_t n_terms, const uint32_t *p
                    "no HIP device");
         DevScope ds(device);
         std::unique_ptr<di_sparse> sp(new di_sparse());
-        sp->device = device;
-        DI_HIP(hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking));
-        sp->own_stream = true;
-        enable_big_lds();
-        DI_HIP(hipFuncSetAttribute((const void *)sparse_score_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)sizeof(SparseShared)));
-        DI_HIP(hipFuncSetAttribute((const void *)sparse_score64_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)sizeof(Sparse64Shared)));
-        DI_HIP(hipFuncSetAttribute((const void *)sparse_merge64_kernel,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)sizeof(Merge64Shared)));
+        sparse_init(*sp, device);
         const int nb = (int)((n_docs + SP_DOCS - 1) / SP_DOCS);
         const int64_t stride = nb + 1;
         std::vector<int64_t> tstart(std::max<int64_t>(n_terms, 1), 0);

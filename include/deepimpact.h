@@ -223,6 +223,49 @@ int di_sparse_info(const di_sparse *sp, int64_t *n_terms, int64_t *n_postings, u
 int di_sparse_timing(di_sparse *sp, const char *name, di_timing *out, int reset);
 int di_sparse_destroy(di_sparse *sp);
 
+/* ---- float index builder: the same index from (term id, impact) pairs per document,
+ * e.g. di_encode's device output, assembled on the device ---- */
+typedef struct di_sparse_builder di_sparse_builder;
+
+int di_sparse_builder_create(int device, di_sparse_builder **out);
+/* Room for n_docs documents and n_pairs kept pairs in all (optional: the pair buffers
+ * grow by reallocation). */
+int di_sparse_builder_reserve(di_sparse_builder *b, int64_t n_docs, int64_t n_pairs);
+/* Appends n_docs documents; document d holds (term_ids[i], impacts[i]) for i in
+ * [cu_terms[d], cu_terms[d + 1]) and gets corpus position *first_doc + d (append order).
+ * Pairs whose impact is not > 0 (-0.0, 0.0, negatives, NaN) are dropped
+ * (nano_beir_evaluator.py:98).  Arguments and flags as di_term_store_append: with
+ * DI_F_DEVICE_PTRS the three arrays are device pointers (impacts = the buffer di_encode
+ * wrote) and only cu_terms is read back.  Runs on hip_stream and waits for it.
+ * cu_terms not starting at 0 or decreasing: DI_EINVAL; more than DI_MAX_SPARSE_DOCS
+ * documents in all: DI_ERANGE (checked before any array is read); after an error the
+ * builder is as it was before the call.  Term ids are checked by finish.
+ * DI_F_TIMING: "sb_append". */
+int di_sparse_builder_append(di_sparse_builder *b, const uint32_t *term_ids,
+                             const float *impacts, const int32_t *cu_terms, int32_t n_docs,
+                             int64_t *first_doc, void *hip_stream, uint32_t flags);
+int di_sparse_builder_info(const di_sparse_builder *b, int64_t *n_docs, int64_t *n_pairs);
+/* The index of everything appended, over terms 0 .. n_terms - 1 (ids used as given; a
+ * term without a kept pair has an empty row): its four device arrays hold the bytes
+ * di_sparse_create uploads for the same postings.  The builder is left unchanged.
+ * Among the kept pairs, a term id >= n_terms or the same term twice in one document
+ * (a repeated (term, doc) posting, as di_sparse_create rejects it): DI_EINVAL (an error
+ * word set on the device and read once at the end, as di_encode reports a bad term
+ * index); no index is returned then.  Runs on hip_stream and waits for it.
+ * DI_F_TIMING: "sb_count", "sb_scan", "sb_scatter", "sb_order" (and the appends'
+ * "sb_append") through di_sparse_timing of the returned index. */
+int di_sparse_builder_finish(di_sparse_builder *b, int64_t n_terms, void *hip_stream,
+                             uint32_t flags, di_sparse **out);
+int di_sparse_builder_destroy(di_sparse_builder *b);
+
+/* Copies the device layout to the host (any pointer may be NULL): term_start[n_terms],
+ * blk_off[n_terms * (n_blocks + 1)], pdoc[n_postings] (doc % 16384), pimp[n_postings];
+ * sizes from di_sparse_info.  Term t's postings of block b are
+ * [term_start[t] + blk_off[t * (n_blocks + 1) + b], term_start[t] + blk_off[.. + b + 1]),
+ * docs ascending. */
+int di_sparse_export(const di_sparse *sp, int64_t *term_start, uint32_t *blk_off,
+                     uint16_t *pdoc, float *pimp);
+
 /* ======================================================================
  * Encoder: DeepImpact forward + first-occurrence gather     (A2, A5-A9)
  * ====================================================================== */
