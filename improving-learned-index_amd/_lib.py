@@ -269,8 +269,70 @@ def csr(queries):
     return flat, cu
 
 
-class DeviceIndex:
+class _Handle:
+    """A native handle in _h, destroyed once by the <_family>_destroy call."""
+
+    _family = ""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._family + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _TimedHandle(_Handle):
+    """A handle whose family reads its DI_F_TIMING regions with <_family>_timing."""
+
+    def timing(self, name, reset=False):
+        t = di_timing()
+        check(getattr(lib(), self._family + "_timing")(self._h, name.encode(), ctypes.byref(t),
+                                                       int(reset)))
+        return t.ms, t.launches
+
+
+def _query_arrays(q_terms, cu_q, k, score_dtype, with_keys):
+    """The inputs and the zeroed outputs of a host search_csr, as the ABI takes them ->
+    (q_terms, cu_q, n_q, docs, scores, n, keys)."""
+    q_terms = np.ascontiguousarray(q_terms, np.uint32)
+    if q_terms.size == 0:
+        q_terms = np.zeros(1, np.uint32)
+    cu_q = np.ascontiguousarray(cu_q, np.int32)
+    n_q = len(cu_q) - 1
+    docs = np.zeros((max(n_q, 1), k), np.uint32)
+    scores = np.zeros((max(n_q, 1), k), score_dtype)
+    n = np.zeros(max(n_q, 1), np.int32)
+    keys = np.zeros((max(n_q, 1), k), np.uint64) if with_keys else None
+    return q_terms, cu_q, n_q, docs, scores, n, keys
+
+
+def _append_arrays(term_ids, impacts, cu_terms, timing):
+    """The (term id, impact) pairs of an append, as the ABI takes them: host numpy arrays
+    made contiguous and checked against cu_terms, torch device tensors as they are ->
+    (term_ids, impacts, cu_terms, n_docs, flags)."""
+    n_docs = len(cu_terms) - 1
+    flags = DI_F_TIMING if timing else 0
+    if _is_device(cu_terms):
+        return term_ids, impacts, cu_terms, n_docs, flags | DI_F_DEVICE_PTRS
+    term_ids = np.ascontiguousarray(term_ids, np.uint32)
+    impacts = np.ascontiguousarray(impacts, np.float32)
+    cu_terms = np.ascontiguousarray(cu_terms, np.int32)
+    if term_ids.size != impacts.size or (n_docs > 0 and term_ids.size < cu_terms[-1]):
+        raise ValueError("term_ids and impacts: one entry per pair of cu_terms")
+    if term_ids.size == 0:
+        term_ids, impacts = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+    return term_ids, impacts, cu_terms, n_docs, flags
+
+
+class DeviceIndex(_TimedHandle):
     """Device-resident quantized index (one shard [doc_lo, doc_hi) of doc ids)."""
+
+    _family = "di_index"
 
     def __init__(self, handle):
         self._h = handle
@@ -303,15 +365,8 @@ class DeviceIndex:
                 "n_blocks": nb.value}
 
     def search_csr(self, q_terms, cu_q, k, with_keys=False, timing=False):
-        q_terms = np.ascontiguousarray(q_terms, np.uint32)
-        if q_terms.size == 0:
-            q_terms = np.zeros(1, np.uint32)
-        cu_q = np.ascontiguousarray(cu_q, np.int32)
-        n_q = len(cu_q) - 1
-        docs = np.zeros((max(n_q, 1), k), np.uint32)
-        scores = np.zeros((max(n_q, 1), k), np.uint32)
-        n = np.zeros(max(n_q, 1), np.int32)
-        keys = np.zeros((max(n_q, 1), k), np.uint64) if with_keys else None
+        q_terms, cu_q, n_q, docs, scores, n, keys = _query_arrays(q_terms, cu_q, k, np.uint32,
+                                                                  with_keys)
         flags = DI_F_TIMING if timing else 0
         check(lib().di_index_search(self._h, ptr(q_terms), ptr(cu_q), n_q, k, ptr(docs),
                                     ptr(scores), ptr(n), ptr(keys), flags))
@@ -354,26 +409,12 @@ class DeviceIndex:
     def sync(self):
         check(lib().di_index_sync(self._h))
 
-    def timing(self, name, reset=False):
-        t = di_timing()
-        check(lib().di_index_timing(self._h, name.encode(), ctypes.byref(t), int(reset)))
-        return t.ms, t.launches
 
-    def close(self):
-        if self._h:
-            lib().di_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TermStore:
+class TermStore(_TimedHandle):
     """Device-resident (term id, impact) lists per passage (di_term_store_*): the
     re-ranker's per-pid cache (reranker.py:39,48-53) on the GPU."""
+
+    _family = "di_term_store"
 
     def __init__(self, device=0, n_docs=0, n_terms=0):
         h = ctypes.c_void_p()
@@ -391,18 +432,8 @@ class TermStore:
         i in [cu_terms[d], cu_terms[d + 1]).  Host numpy arrays, or torch device tensors
         (all three; term ids as int32 bit patterns).  Returns the store index of the first
         appended passage."""
-        n_docs = len(cu_terms) - 1
-        flags = DI_F_TIMING if timing else 0
-        if _is_device(cu_terms):
-            flags |= DI_F_DEVICE_PTRS
-        else:
-            term_ids = np.ascontiguousarray(term_ids, np.uint32)
-            impacts = np.ascontiguousarray(impacts, np.float32)
-            cu_terms = np.ascontiguousarray(cu_terms, np.int32)
-            if term_ids.size != impacts.size or (n_docs > 0 and term_ids.size < cu_terms[-1]):
-                raise ValueError("term_ids and impacts: one entry per pair of cu_terms")
-            if term_ids.size == 0:
-                term_ids, impacts = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        term_ids, impacts, cu_terms, n_docs, flags = _append_arrays(term_ids, impacts, cu_terms,
+                                                                    timing)
         first = I64(0)
         check(lib().di_term_store_append(self._h, ptr(term_ids), ptr(impacts), ptr(cu_terms),
                                          n_docs, ctypes.byref(first),
@@ -448,22 +479,6 @@ class TermStore:
         check(lib().di_term_store_info(self._h, ctypes.byref(nd), ctypes.byref(nt),
                                        ctypes.byref(nb)))
         return {"n_docs": nd.value, "n_terms": nt.value, "device_bytes": nb.value}
-
-    def timing(self, name, reset=False):
-        t = di_timing()
-        check(lib().di_term_store_timing(self._h, name.encode(), ctypes.byref(t), int(reset)))
-        return t.ms, t.launches
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().di_term_store_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def topk_merge(keys, counts, k, device=0, stream=None, flags=0):
@@ -714,8 +729,10 @@ def format_impact_lines(doc_terms, doc_impacts):
     return out.raw[:n.value].decode("utf-8")
 
 
-class DeviceSparseIndex:
+class DeviceSparseIndex(_TimedHandle):
     """Device-resident float index (di_sparse_*), NanoBEIR's SparseSearch path."""
+
+    _family = "di_sparse"
 
     def __init__(self, term_off, pdoc, pimp, n_docs, device=0):
         term_off = np.ascontiguousarray(term_off, np.int64)
@@ -756,33 +773,19 @@ class DeviceSparseIndex:
                                      ptr(pimp)))
         return term_start, blk_off, pdoc, pimp
 
-    def timing(self, name, reset=False):
-        t = di_timing()
-        check(lib().di_sparse_timing(self._h, name.encode(), ctypes.byref(t), int(reset)))
-        return t.ms, t.launches
-
     def search_csr(self, q_terms, cu_q, k, with_keys=False, accumulation="f32"):
         """accumulation "f32" (numpy >= 2) or "f64" (the reference's pinned numpy 1.25:
         f64 scores; no keys)."""
-        q_terms = np.ascontiguousarray(q_terms, np.uint32)
-        if q_terms.size == 0:
-            q_terms = np.zeros(1, np.uint32)
-        cu_q = np.ascontiguousarray(cu_q, np.int32)
-        n_q = len(cu_q) - 1
-        docs = np.zeros((max(n_q, 1), k), np.uint32)
+        if accumulation not in ("f32", "f64"):
+            raise ValueError(f"accumulation must be 'f32' or 'f64', not {accumulation!r}")
+        if accumulation == "f64" and with_keys:
+            raise ValueError("f64 search has no 64-bit merge keys")
+        q_terms, cu_q, n_q, docs, scores, n, keys = _query_arrays(
+            q_terms, cu_q, k, np.float64 if accumulation == "f64" else np.float32, with_keys)
         if accumulation == "f64":
-            if with_keys:
-                raise ValueError("f64 search has no 64-bit merge keys")
-            scores = np.zeros((max(n_q, 1), k), np.float64)
-            n = np.zeros(max(n_q, 1), np.int32)
             check(lib().di_sparse_search_f64(self._h, ptr(q_terms), ptr(cu_q), n_q, k, ptr(docs),
                                              ptr(scores), ptr(n), 0))
             return docs[:n_q], scores[:n_q], n[:n_q], None
-        if accumulation != "f32":
-            raise ValueError(f"accumulation must be 'f32' or 'f64', not {accumulation!r}")
-        scores = np.zeros((max(n_q, 1), k), np.float32)
-        n = np.zeros(max(n_q, 1), np.int32)
-        keys = np.zeros((max(n_q, 1), k), np.uint64) if with_keys else None
         check(lib().di_sparse_search(self._h, ptr(q_terms), ptr(cu_q), n_q, k, ptr(docs),
                                      ptr(scores), ptr(n), ptr(keys), 0))
         return docs[:n_q], scores[:n_q], n[:n_q], (keys[:n_q] if with_keys else None)
@@ -793,22 +796,13 @@ class DeviceSparseIndex:
         return [list(zip(docs[i, :n[i]].tolist(), scores[i, :n[i]].tolist()))
                 for i in range(len(queries))]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().di_sparse_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SparseBuilder:
+class SparseBuilder(_Handle):
     """Device builder of the float index (di_sparse_builder_*): documents appended as
     (term id, impact) pairs -- host arrays, or the device buffers of an encode step --
     and assembled into a DeviceSparseIndex on the GPU."""
+
+    _family = "di_sparse_builder"
 
     def __init__(self, device=0, n_docs=0, n_pairs=0):
         h = ctypes.c_void_p()
@@ -826,18 +820,8 @@ class SparseBuilder:
         for i in [cu_terms[d], cu_terms[d + 1]); pairs whose impact is not > 0 are dropped.
         Host numpy arrays, or torch device tensors (all three; term ids as int32 bit
         patterns).  Returns the corpus position of the first appended document."""
-        n_docs = len(cu_terms) - 1
-        flags = DI_F_TIMING if timing else 0
-        if _is_device(cu_terms):
-            flags |= DI_F_DEVICE_PTRS
-        else:
-            term_ids = np.ascontiguousarray(term_ids, np.uint32)
-            impacts = np.ascontiguousarray(impacts, np.float32)
-            cu_terms = np.ascontiguousarray(cu_terms, np.int32)
-            if term_ids.size != impacts.size or (n_docs > 0 and term_ids.size < cu_terms[-1]):
-                raise ValueError("term_ids and impacts: one entry per pair of cu_terms")
-            if term_ids.size == 0:
-                term_ids, impacts = np.zeros(1, np.uint32), np.zeros(1, np.float32)
+        term_ids, impacts, cu_terms, n_docs, flags = _append_arrays(term_ids, impacts, cu_terms,
+                                                                    timing)
         first = I64(0)
         check(lib().di_sparse_builder_append(self._h, ptr(term_ids), ptr(impacts),
                                              ptr(cu_terms), n_docs, ctypes.byref(first),
@@ -856,14 +840,3 @@ class SparseBuilder:
         check(lib().di_sparse_builder_finish(self._h, int(n_terms), ctypes.c_void_p(stream or 0),
                                              DI_F_TIMING if timing else 0, ctypes.byref(h)))
         return DeviceSparseIndex._from_handle(h)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().di_sparse_builder_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

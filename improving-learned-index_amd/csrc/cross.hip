@@ -169,24 +169,6 @@ __global__ __launch_bounds__(SORT_THREADS) void segment_order_kernel(
         out_pos[o + i] = (int32_t)~(uint32_t)keys[i];
 }
 
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != dev) DI_HIP(hipSetDevice(dev));
-    }
-    ~DeviceScope() {
-        int cur;
-        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-void check_device(int device) {
-    int ndev = 0;
-    DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV, "no HIP device");
-    DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
-}
-
 int check_format(const di_pair_format *f) {  // -> the content budget of a sequence
     DI_REQUIRE(f, DI_EINVAL, "null format");
     DI_REQUIRE(f->n_prefix >= 0 && f->n_prefix <= DI_MAX_PAIR_SPECIALS && f->n_suffix >= 0 &&
@@ -220,12 +202,12 @@ struct StagedPairs {
             DI_REQUIRE((nd == 0 || doc_tok) && (nq == 0 || qry_tok), DI_EINVAL,
                        "null token store");
         }
-        a.doc_tok = (const int32_t *)stage_in(doc_tok, nd * 4, dev, dt, s);
-        a.doc_off = (const int64_t *)stage_in(doc_off, (size_t)(n_docs + 1) * 8, dev, dof, s);
-        a.qry_tok = (const int32_t *)stage_in(qry_tok, nq * 4, dev, qt, s);
-        a.qry_off = (const int64_t *)stage_in(qry_off, (size_t)(n_q + 1) * 8, dev, qof, s);
-        a.pair_doc = (const int32_t *)stage_in(pair_doc, (size_t)n_pairs * 4, dev, pd, s);
-        a.pair_qry = (const int32_t *)stage_in(pair_qry, (size_t)n_pairs * 4, dev, pq, s);
+        a.doc_tok = stage_in(doc_tok, nd, dev, dt, s);
+        a.doc_off = stage_in(doc_off, (size_t)n_docs + 1, dev, dof, s);
+        a.qry_tok = stage_in(qry_tok, nq, dev, qt, s);
+        a.qry_off = stage_in(qry_off, (size_t)n_q + 1, dev, qof, s);
+        a.pair_doc = stage_in(pair_doc, (size_t)n_pairs, dev, pd, s);
+        a.pair_qry = stage_in(pair_qry, (size_t)n_pairs, dev, pq, s);
         a.n_docs = n_docs;
         a.n_q = n_q;
         a.n_pairs = n_pairs;
@@ -242,8 +224,7 @@ void launch_scan(const PairArgs &a, const di_pair_format &f, int budget, int32_t
 // The size read-back: the one synchronisation of a pack.
 void read_info(const int64_t *d_info, hipStream_t s, int64_t *n_tokens, int32_t *max_len) {
     int64_t info[3] = {0, 0, 0};
-    DI_HIP(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, s));
-    DI_HIP(hipStreamSynchronize(s));
+    read_back(info, d_info, s);
     DI_REQUIRE(!(info[2] & PK_BAD_INDEX), DI_EINVAL,
                "a pair index is outside its token store (or the store's offsets decrease)");
     DI_REQUIRE(!(info[2] & PK_TOO_LONG), DI_ERANGE, "the packed batch has %lld tokens >= 2^31",
@@ -285,29 +266,16 @@ int di_pairs_pack(const int32_t *doc_tok, const int64_t *doc_off, int32_t n_docs
         StagedPairs sp;
         sp.stage(doc_tok, doc_off, n_docs, qry_tok, qry_off, n_q, pair_doc, pair_qry, n_pairs,
                  dev, s);
-        DevBuf info, cu, ids;
+        DevBuf info, b_cu, b_ids;
         info.reserve(24);
-        int32_t *d_cu = cu_seqlens, *d_ids = tok_ids;
-        if (!dev) {
-            cu.reserve((size_t)(n_pairs + 1) * 4);
-            d_cu = cu.as<int32_t>();
-        }
-        launch_scan(sp.a, *fmt, budget, d_cu, nullptr, nullptr, info.as<int64_t>(), s);
+        StagedOut<int32_t> cu(cu_seqlens, (size_t)n_pairs + 1, dev, b_cu), ids(tok_ids, dev, b_ids);
+        launch_scan(sp.a, *fmt, budget, cu.d, nullptr, nullptr, info.as<int64_t>(), s);
         read_info(info.as<int64_t>(), s, n_tokens, max_len);
         DI_REQUIRE(*n_tokens <= tok_cap, DI_ERANGE, "tok_ids holds %lld tokens, %lld needed",
                    (long long)tok_cap, (long long)*n_tokens);
-        if (!dev) {
-            ids.reserve((size_t)*n_tokens * 4);
-            d_ids = ids.as<int32_t>();
-        }
-        launch_copy(sp.a, *fmt, d_cu, d_ids, s);
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(cu_seqlens, d_cu, (size_t)(n_pairs + 1) * 4,
-                                  hipMemcpyDeviceToHost, s));
-            if (*n_tokens)
-                DI_HIP(hipMemcpyAsync(tok_ids, d_ids, (size_t)*n_tokens * 4,
-                                      hipMemcpyDeviceToHost, s));
-        }
+        launch_copy(sp.a, *fmt, cu.d, ids.size((size_t)*n_tokens), s);
+        cu.copy_back(s);
+        ids.copy_back(s);
         // (host pointers, or staged temporaries that die with this call: wait)
         if (!dev || !(flags & DI_F_ASYNC)) DI_HIP(hipStreamSynchronize(s));
     });
@@ -353,23 +321,16 @@ int di_encode_pairs(di_encoder *e, const int32_t *doc_tok, const int64_t *doc_of
             launch_copy(sp.a, *fmt, e->cu.as<int32_t>(), e->ids.as<int32_t>(), s);
         }
         DevBuf tmp;
-        float *d_out = out_scores;
-        if (!dev) {
-            tmp.reserve((size_t)n_pairs * 4);
-            d_out = tmp.as<float>();
-        }
+        StagedOut<float> out(out_scores, (size_t)n_pairs, dev, tmp);
         // the staged stores are temporaries of this call: a host-pointer call waits
         const uint32_t f2 = DI_F_DEVICE_PTRS | (timing ? DI_F_TIMING : 0u) |
                             (dev && (flags & DI_F_ASYNC) ? DI_F_ASYNC : 0u);
         const int rc = di_encode(e, e->ids.as<int32_t>(), e->cu.as<int32_t>(), n_pairs, n_tokens,
                                  max_len, e->tt.as<int32_t>(), e->cut.as<int32_t>(), n_pairs,
-                                 d_out, f2);
+                                 out.d, f2);
         if (rc != DI_OK) throw Error{rc};  // (di_last_error holds di_encode's message)
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_scores, d_out, (size_t)n_pairs * 4, hipMemcpyDeviceToHost,
-                                  s));
-            DI_HIP(hipStreamSynchronize(s));
-        }
+        out.copy_back(s);
+        if (!dev) DI_HIP(hipStreamSynchronize(s));
     });
 }
 
@@ -384,35 +345,23 @@ int di_segment_order(const float *scores, const int32_t *cu_seg, int32_t n_seg, 
         if (n_seg == 0) return;
         int64_t n = 0;
         if (!dev) {
-            DI_REQUIRE(cu_seg[0] == 0, DI_EINVAL, "cu_seg[0] must be 0");
-            for (int i = 0; i < n_seg; ++i) {
-                const int64_t len = (int64_t)cu_seg[i + 1] - cu_seg[i];
-                DI_REQUIRE(len >= 0, DI_EINVAL, "cu_seg not monotone at %d", i);
-                DI_REQUIRE(len <= DI_MAX_TOPK, DI_ERANGE, "segment %d has %lld scores > %d", i,
-                           (long long)len, DI_MAX_TOPK);
-            }
-            n = cu_seg[n_seg];
+            n = check_cu(cu_seg, n_seg, "cu_seg", DI_MAX_TOPK);
             if (n == 0) return;
         }
         DI_REQUIRE(scores && out_pos, DI_EINVAL, "null argument");
-        DevBuf sc, cu, pos, err;
+        DevBuf sc, cu, b_pos, err;
         err.reserve(8);
         DI_HIP(hipMemsetAsync(err.p, 0, 8, s));
-        const float *d_sc = (const float *)stage_in(scores, (size_t)n * 4, dev, sc, s);
-        const int32_t *d_cu = (const int32_t *)stage_in(cu_seg, (size_t)(n_seg + 1) * 4, dev, cu, s);
-        int32_t *d_pos = out_pos;
-        if (!dev) {
-            pos.reserve((size_t)n * 4);
-            d_pos = pos.as<int32_t>();
-        }
+        const float *d_sc = stage_in(scores, (size_t)n, dev, sc, s);
+        const int32_t *d_cu = stage_in(cu_seg, (size_t)n_seg + 1, dev, cu, s);
+        StagedOut<int32_t> pos(out_pos, (size_t)n, dev, b_pos);
         hipLaunchKernelGGL(segment_order_kernel, dim3(n_seg), dim3(SORT_THREADS), 0, s, d_sc,
-                           d_cu, d_pos, err.as<int32_t>());
+                           d_cu, pos.d, err.as<int32_t>());
         check_launch("segment_order");
-        if (!dev) DI_HIP(hipMemcpyAsync(out_pos, d_pos, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        pos.copy_back(s);
         // (the error words are a temporary of this call: it always waits for them)
         int32_t h[2] = {0, 0};
-        DI_HIP(hipMemcpyAsync(h, err.p, 8, hipMemcpyDeviceToHost, s));
-        DI_HIP(hipStreamSynchronize(s));
+        read_back(h, err.p, s);
         DI_REQUIRE(!h[0], DI_EINVAL, "cu_seg is not monotone");
         DI_REQUIRE(!h[1], DI_ERANGE, "a segment has more than %d scores", DI_MAX_TOPK);
     });

@@ -1,6 +1,7 @@
 // di_common.h -- shared host-side plumbing of libdeepimpact_hip.so:
 // error reporting across the C ABI, HIP checks, device buffers, per-kernel
-// HIP-event timing.  gfx950 only.
+// HIP-event timing, and what every entry point does with its arguments (device
+// scope, staging in and out, small read-backs, offset checks).  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -272,13 +274,93 @@ inline void check_launch(const char *what) {
     }
 }
 
-// Copy `bytes` from a host or device pointer into a device buffer on stream s.
-inline const void *stage_in(const void *src, size_t bytes, bool device_ptrs, DevBuf &buf,
-                            hipStream_t s) {
-    if (device_ptrs || bytes == 0) return src;
-    buf.reserve(bytes);
-    DI_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s));
-    return buf.p;
+// The current device set to `dev` for a scope, and put back after it.
+struct DeviceScope {
+    int prev = -1;
+    explicit DeviceScope(int dev) {
+        DI_HIP(hipGetDevice(&prev));
+        if (prev != dev) DI_HIP(hipSetDevice(dev));
+    }
+    DeviceScope(const DeviceScope &) = delete;
+    ~DeviceScope() {
+        int cur;
+        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+inline void check_device(int device) {
+    int ndev = 0;
+    DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV, "no HIP device");
+    DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
+}
+
+// The `n` elements at a host or device pointer, as a device array: a device pointer (or
+// nothing) as it is, a host array copied into `buf` on stream s.
+template <class T>
+const T *stage_in(const T *src, size_t n, bool device_ptrs, DevBuf &buf, hipStream_t s) {
+    if (device_ptrs || n == 0) return src;
+    buf.reserve(n * sizeof(T));
+    DI_HIP(hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+    return buf.as<T>();
+}
+
+// An output array of the caller's.  d is where kernels write it: the caller's own pointer
+// when that is a device one, else `buf`, which copy_back() copies to the caller's host
+// array.  The element count may come later than the constructor, through size().
+template <class T>
+struct StagedOut {
+    T *out, *d = nullptr;
+    size_t n = 0;
+    bool dev;
+    DevBuf &buf;
+    StagedOut(T *out_, bool dev_, DevBuf &buf_) : out(out_), dev(dev_), buf(buf_) {}
+    StagedOut(T *out_, size_t n_, bool dev_, DevBuf &buf_) : StagedOut(out_, dev_, buf_) {
+        size(n_);
+    }
+    T *size(size_t n_) {
+        n = n_;
+        if (dev || !out) return d = out;  // (an optional output left out stays null)
+        buf.reserve(n * sizeof(T));
+        return d = buf.as<T>();
+    }
+    void copy_back(hipStream_t s) const {  // (enqueued: the caller waits for s)
+        if (!dev && out && n) DI_HIP(hipMemcpyAsync(out, d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    }
+};
+
+// One value or one small fixed array read from the device on stream s: waits for s, and
+// resolves `timer` after the wait when one is given.
+template <class T>
+void read_back(T &host, const void *d_src, hipStream_t s, Timer *timer = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value, "read_back copies bytes");
+    DI_HIP(hipMemcpyAsync(&host, d_src, sizeof(T), hipMemcpyDeviceToHost, s));
+    DI_HIP(hipStreamSynchronize(s));
+    if (timer) timer->resolve();
+}
+
+// The n + 1 offsets `cu` of n segments, checked on the host: cu[0] == 0, none decreases,
+// and no segment is longer than `cap` (when cap >= 0).  -> cu[n], the total.
+template <class I>
+int64_t check_cu(const I *cu, int64_t n, const char *name, int64_t cap = -1) {
+    DI_REQUIRE(cu[0] == 0, DI_EINVAL, "%s[0] must be 0", name);
+    for (int64_t i = 0; i < n; ++i) {
+        DI_REQUIRE(cu[i + 1] >= cu[i], DI_EINVAL, "%s not monotone at %lld", name, (long long)i);
+        const int64_t len = (int64_t)cu[i + 1] - (int64_t)cu[i];  // (both >= 0 here)
+        DI_REQUIRE(cap < 0 || len <= cap, DI_ERANGE, "%s: segment %lld has %lld entries > %lld",
+                   name, (long long)i, (long long)len, (long long)cap);
+    }
+    return (int64_t)cu[n];
+}
+
+// The n + 1 offsets `cu` where the host can read them: a host array as it is, a device
+// array copied into `h` on stream s (waits for s).
+template <class I>
+const I *host_cu(const I *cu, int64_t n, bool device_ptrs, std::vector<I> &h, hipStream_t s) {
+    if (!device_ptrs) return cu;
+    h.resize((size_t)n + 1);
+    DI_HIP(hipMemcpyAsync(h.data(), cu, h.size() * sizeof(I), hipMemcpyDeviceToHost, s));
+    DI_HIP(hipStreamSynchronize(s));
+    return h.data();
 }
 
 // `buf` with room for `need` bytes, its first `used` bytes kept.  Waits for s.

@@ -641,30 +641,21 @@ extern "C" int di_quantize(const float *impacts, int64_t n, double max_val, int3
     return guard([&] {
         DI_REQUIRE(impacts && out && n >= 0 && bits >= 1 && bits <= 16, DI_EINVAL,
                    "bad argument");
-        int prev = 0;
-        DI_HIP(hipGetDevice(&prev));
-        DI_HIP(hipSetDevice(device));
+        DeviceScope ds(device);
         hipStream_t s = (hipStream_t)hip_stream;
         const bool dev = flags & DI_F_DEVICE_PTRS;
         DevBuf bin, bout, bmax;
         bmax.reserve(16);
-        const float *d_in = (const float *)stage_in(impacts, (size_t)n * 4, dev, bin, s);
-        int32_t *d_out = out;
-        if (!dev) {
-            bout.reserve((size_t)std::max<int64_t>(n, 1) * 4);
-            d_out = bout.as<int32_t>();
-        }
-        launch_quantize(d_in, n, max_val, bits, d_out, bmax.as<unsigned int>(), s);
+        const float *d_in = stage_in(impacts, (size_t)n, dev, bin, s);
+        StagedOut<int32_t> q(out, (size_t)n, dev, bout);
+        launch_quantize(d_in, n, max_val, bits, q.d, bmax.as<unsigned int>(), s);
+        q.copy_back(s);
         unsigned int mb = 0;
-        DI_HIP(hipMemcpyAsync(&mb, bmax.p, 4, hipMemcpyDeviceToHost, s));
-        if (!dev && n)
-            DI_HIP(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        DI_HIP(hipStreamSynchronize(s));
+        read_back(mb, bmax.p, s);
         float mf;
         std::memcpy(&mf, &mb, 4);
         if (max_used) *max_used = max_val > 0.0 ? max_val : (double)mf;
         DI_REQUIRE(max_val > 0.0 || n == 0 || mf > 0.f, DI_EINVAL,
                    "max impact is 0: the reference divides by zero (quantize.py:37)");
-        (void)hipSetDevice(prev);
     });
 }

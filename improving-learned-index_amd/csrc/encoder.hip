@@ -92,18 +92,6 @@ using namespace di;
 
 namespace {
 
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != dev) DI_HIP(hipSetDevice(dev));
-    }
-    ~DeviceScope() {
-        int cur;
-        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 uint16_t f32_to_bf16_bits(float f) {  // round to nearest even (NaN stays NaN)
     uint32_t u;
     std::memcpy(&u, &f, 4);
@@ -858,15 +846,13 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
         out = e->ent_single.as<float>();
         out_pair = e->ent_pair.as<float>();
     }
-    const int32_t *d_ids =
-        (const int32_t *)stage_in(tok_ids, (size_t)n_tokens * 4, dev, e->ids, s);
-    const int32_t *d_cu =
-        (const int32_t *)stage_in(cu_seqlens, (size_t)(n_docs + 1) * 4, dev, e->cu, s);
+    const int32_t *d_ids = stage_in(tok_ids, (size_t)n_tokens, dev, e->ids, s);
+    const int32_t *d_cu = stage_in(cu_seqlens, (size_t)n_docs + 1, dev, e->cu, s);
     DI_HIP(hipMemsetAsync(e->err.p, 0, 4, s));
     const int32_t *d_tt = nullptr, *d_cut = nullptr;
     if (!token_out) {
-        d_tt = (const int32_t *)stage_in(term_tok, (size_t)n_terms * 4, dev, e->tt, s);
-        d_cut = (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, e->cut, s);
+        d_tt = stage_in(term_tok, (size_t)n_terms, dev, e->tt, s);
+        d_cut = stage_in(cu_terms, (size_t)n_docs + 1, dev, e->cut, s);
     }
     // pairwise: check the arrays on the device too (the only check of device
     // pointers), lay out and clear Mx, and let the forwards call pair_attn_kernel
@@ -883,8 +869,7 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
                    "pairwise: %lld term-pair slots in one batch (limit 2^32)",
                    (long long)mx_need);
         e->Mx.reserve((size_t)std::max<int64_t>(mx_need, 1) * 4);
-        d_cup = (const int64_t *)stage_in(pc->cu_pairs, (size_t)(n_docs + 1) * 8, dev, e->cup,
-                                          s);
+        d_cup = stage_in(pc->cu_pairs, (size_t)n_docs + 1, dev, e->cup, s);
         {
             TimedLaunch tl(e->timer, timing, "pair_prep", s);
             if (mx_need) DI_HIP(hipMemsetAsync(e->Mx.p, 0, (size_t)mx_need * 4, s));
@@ -974,9 +959,7 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
     }
     if (!(flags & DI_F_ASYNC) || !dev) {
         int32_t err = 0;
-        DI_HIP(hipMemcpyAsync(&err, e->err.p, 4, hipMemcpyDeviceToHost, s));
-        DI_HIP(hipStreamSynchronize(s));
-        e->timer.resolve();
+        read_back(err, e->err.p, s, &e->timer);
         DI_REQUIRE(!(err & 1), DI_EINVAL,
                    "a token id is outside the vocabulary or a position exceeds the table");
         DI_REQUIRE(!(err & 2), DI_EINVAL, "a term token index is outside its document");
@@ -995,10 +978,7 @@ int di_encoder_create(const di_encoder_cfg *cfg, const di_tensor *w, int32_t n_w
                       di_encoder **out) {
     return guard([&] {
         DI_REQUIRE(cfg && out && (n_w == 0 || w), DI_EINVAL, "null argument");
-        int ndev = 0;
-        DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV,
-                   "no HIP device");
-        DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
+        check_device(device);
         const di_encoder_cfg &c = *cfg;
         DI_REQUIRE(c.variant == DI_VARIANT_XLMR || c.variant == DI_VARIANT_BERT, DI_EINVAL,
                    "bad variant");
@@ -1225,7 +1205,7 @@ int di_encode_pairwise_entries(di_encoder *e, const int32_t *tok_ids, const int3
         const int64_t *d_cp = dev || n_docs == 0 ? cu_pairs : e->cup.as<int64_t>();
         const int32_t *d_sp = nullptr;
         if (single_pos && n_terms > 0)
-            d_sp = (const int32_t *)stage_in(single_pos, (size_t)n_terms * 4, dev, e->ent_pos, s);
+            d_sp = stage_in(single_pos, (size_t)n_terms, dev, e->ent_pos, s);
         pairwise_order_run(e->order, &e->timer, flags & DI_F_TIMING, e->ent_single.as<float>(),
                            e->ent_pair.as<float>(), d_ct, d_cp, d_sp, n_docs, n_terms, n_pairs,
                            out_cu, out_first, out_second, out_score, out_cap, n_out, dev,

@@ -23,18 +23,6 @@
 namespace di {
 namespace {
 
-struct XDevice {
-    int prev = -1;
-    explicit XDevice(int dev) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != dev) DI_HIP(hipSetDevice(dev));
-    }
-    ~XDevice() {
-        int cur;
-        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // samples[q][j] = keys[q][(j + 1) g - 1] when inside the query's valid prefix, else 0
 __global__ void xchg_sample_kernel(const uint64_t *__restrict__ keys,
                                    const int32_t *__restrict__ counts, int n_q, int k, int g,
@@ -187,7 +175,7 @@ int di_xchg_sample(const uint64_t *keys, const int32_t *counts, int32_t n_q, int
         DI_REQUIRE(keys && counts && samples && n_q >= 0 && k > 0 && g > 0 && g <= k,
                    DI_EINVAL, "bad argument");
         if (n_q == 0) return;
-        XDevice ds(device);
+        DeviceScope ds(device);
         const int s_n = k / g;
         hipLaunchKernelGGL(xchg_sample_kernel, dim3(grid_of((int64_t)n_q * s_n, 256)), dim3(256),
                            0, (hipStream_t)hip_stream, keys, counts, n_q, k, g, s_n, samples);
@@ -203,7 +191,7 @@ int di_xchg_count(const uint64_t *gathered_samples, int32_t world, const uint64_
                        g > 0 && g <= k,
                    DI_EINVAL, "bad argument");
         if (n_q == 0) return;
-        XDevice ds(device);
+        DeviceScope ds(device);
         const int need = (k + g - 1) / g;
         hipLaunchKernelGGL(xchg_count_kernel, dim3(grid_of(n_q, 4)), dim3(256), 0,
                            (hipStream_t)hip_stream, gathered_samples, world, k / g, keys, counts,
@@ -217,7 +205,7 @@ int di_xchg_offsets(const int32_t *gathered_ec, int32_t world, int32_t n_q, int6
     return guard([&] {
         DI_REQUIRE(gathered_ec && offsets && totals && world > 0 && n_q >= 0, DI_EINVAL,
                    "bad argument");
-        XDevice ds(device);
+        DeviceScope ds(device);
         hipLaunchKernelGGL(xchg_offsets_kernel, dim3(world), dim3(XS_T), 0,
                            (hipStream_t)hip_stream, gathered_ec, n_q, offsets, totals);
         check_launch("xchg_offsets");
@@ -229,7 +217,7 @@ int di_xchg_pack(const uint64_t *keys, const int32_t *ec, const int64_t *offsets
     return guard([&] {
         DI_REQUIRE(keys && ec && offsets && buf && n_q >= 0 && k > 0, DI_EINVAL, "bad argument");
         if (n_q == 0) return;
-        XDevice ds(device);
+        DeviceScope ds(device);
         hipLaunchKernelGGL(xchg_pack_kernel, dim3(grid_of(n_q, 4)), dim3(256), 0,
                            (hipStream_t)hip_stream, keys, ec, offsets, n_q, k, buf);
         check_launch("xchg_pack");
@@ -244,7 +232,7 @@ int di_xchg_unpack(const uint64_t *gathered, int64_t emax, const int32_t *gather
                        k > 0 && emax >= 0 && (gathered || emax == 0),
                    DI_EINVAL, "bad argument");
         if (n_q == 0) return;
-        XDevice ds(device);
+        DeviceScope ds(device);
         hipLaunchKernelGGL(xchg_unpack_kernel, dim3(grid_of((int64_t)world * n_q, 4)), dim3(256),
                            0, (hipStream_t)hip_stream, gathered, emax, gathered_ec, offsets,
                            world, n_q, k, out_keys, out_n);

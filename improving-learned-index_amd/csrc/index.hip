@@ -2357,18 +2357,6 @@ struct di_index {
 
 namespace {
 
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != dev) DI_HIP(hipSetDevice(dev));
-    }
-    ~DeviceScope() {
-        int cur;
-        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 template <class T>
 void upload(DevBuf &d, const std::vector<T> &h) {
     d.reserve(std::max<size_t>(h.size() * sizeof(T), 16));
@@ -2779,10 +2767,7 @@ int di_index_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pd
     return guard([&] {
         DI_REQUIRE(out && term_off && (n_terms == 0 || (pdoc && pval)), DI_EINVAL,
                    "null argument");
-        int ndev = 0;
-        DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV,
-                   "no HIP device");
-        DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
+        check_device(device);
         DeviceScope ds(device);
         std::unique_ptr<di_index> ix(new di_index());
         ix->device = device;
@@ -2972,25 +2957,12 @@ int di_index_search(di_index *ix, const uint32_t *q_terms, const int32_t *cu_q, 
         const size_t rec_bytes = (size_t)chunk * rec_per_q;
         const bool use_rec = !(ix->ablate & 1024);
         if (use_rec) ix->ws_rec.reserve(rec_bytes);
-        const uint32_t *dq = (const uint32_t *)stage_in(
-            q_terms, (size_t)nterms_total * 4, dev, ix->ws_q, s);
-        const int32_t *dcu =
-            (const int32_t *)stage_in(cu_q, (size_t)(n_q + 1) * 4, dev, ix->ws_cu, s);
-        uint32_t *ddoc = out_doc, *dscore = out_score;
-        int32_t *dn = out_n;
-        uint64_t *dkey = out_key;
-        if (!dev) {
-            ix->ws_doc.reserve((size_t)n_q * k * 4);
-            ix->ws_score.reserve((size_t)n_q * k * 4);
-            ix->ws_n.reserve((size_t)n_q * 4);
-            ddoc = ix->ws_doc.as<uint32_t>();
-            dscore = ix->ws_score.as<uint32_t>();
-            dn = ix->ws_n.as<int32_t>();
-            if (out_key) {
-                ix->ws_key.reserve((size_t)n_q * k * 8);
-                dkey = ix->ws_key.as<uint64_t>();
-            }
-        }
+        const uint32_t *dq = stage_in(q_terms, (size_t)nterms_total, dev, ix->ws_q, s);
+        const int32_t *dcu = stage_in(cu_q, (size_t)n_q + 1, dev, ix->ws_cu, s);
+        const size_t nk = (size_t)n_q * k;
+        StagedOut<uint32_t> doc(out_doc, nk, dev, ix->ws_doc), score(out_score, nk, dev, ix->ws_score);
+        StagedOut<int32_t> on(out_n, (size_t)n_q, dev, ix->ws_n);
+        StagedOut<uint64_t> key(out_key, nk, dev, ix->ws_key);
         for (int q0 = 0; q0 < n_q; q0 += chunk) {
             const int nq = std::min(chunk, n_q - q0);
             if (ix->nb == 0) {
@@ -3074,20 +3046,15 @@ int di_index_search(di_index *ix, const uint32_t *q_terms, const int32_t *cu_q, 
             {
                 TimedLaunch tl(ix->timer, timing, "merge_topk", s);
                 launch_merge(ix->ws_ck.as<uint64_t>(), ix->ws_cn.as<int32_t>(), nq, nb, kl, k,
-                             dkey ? dkey + (int64_t)q0 * k : nullptr, ddoc + (int64_t)q0 * k,
-                             dscore + (int64_t)q0 * k, dn + q0, DECODE_QUANT, s, false,
+                             key.d ? key.d + (int64_t)q0 * k : nullptr, doc.d + (int64_t)q0 * k,
+                             score.d + (int64_t)q0 * k, on.d + q0, DECODE_QUANT, s, false,
                              dcu + q0);
             }
         }
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_doc, ddoc, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_score, dscore, (size_t)n_q * k * 4, hipMemcpyDeviceToHost,
-                                  s));
-            DI_HIP(hipMemcpyAsync(out_n, dn, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
-            if (out_key)
-                DI_HIP(hipMemcpyAsync(out_key, dkey, (size_t)n_q * k * 8, hipMemcpyDeviceToHost,
-                                      s));
-        }
+        doc.copy_back(s);
+        score.copy_back(s);
+        on.copy_back(s);
+        key.copy_back(s);
         if (ix->ablate & 64) {
             unsigned long long ph[12];
             DI_HIP(hipStreamSynchronize(s));
@@ -3328,8 +3295,7 @@ int di_index_timing(di_index *ix, const char *name, di_timing *out, int reset) {
             DeviceScope ds(ix->device);
             unsigned long long st[2] = {0, 0};
             if (ix->bm_stat.p) {
-                DI_HIP(hipStreamSynchronize(ix->stream));
-                DI_HIP(hipMemcpy(st, ix->bm_stat.p, 16, hipMemcpyDeviceToHost));
+                read_back(st, ix->bm_stat.p, ix->stream);
                 if (reset) DI_HIP(hipMemset(ix->bm_stat.p, 0, 16));
             }
             out->ms = 0.0;
@@ -3364,24 +3330,14 @@ int di_topk_merge(const uint64_t *keys, const int32_t *counts, int32_t n_q, int3
         hipStream_t s = (hipStream_t)hip_stream;
         const bool dev = flags & DI_F_DEVICE_PTRS;
         DevBuf bk, bc, bo, bn;
-        const uint64_t *dk = (const uint64_t *)stage_in(keys, (size_t)n_q * n_lists * k * 8, dev,
-                                                        bk, s);
-        const int32_t *dc = (const int32_t *)stage_in(counts, (size_t)n_q * n_lists * 4, dev, bc,
-                                                      s);
-        uint64_t *dok = out_key;
-        int32_t *don = out_n;
-        if (!dev) {
-            bo.reserve((size_t)n_q * k * 8);
-            bn.reserve((size_t)n_q * 4);
-            dok = bo.as<uint64_t>();
-            don = bn.as<int32_t>();
-        }
-        launch_merge(dk, dc, n_q, n_lists, k, k, dok, nullptr, nullptr, don, DECODE_NONE, s,
+        const uint64_t *dk = stage_in(keys, (size_t)n_q * n_lists * k, dev, bk, s);
+        const int32_t *dc = stage_in(counts, (size_t)n_q * n_lists, dev, bc, s);
+        StagedOut<uint64_t> ok(out_key, (size_t)n_q * k, dev, bo);
+        StagedOut<int32_t> on(out_n, (size_t)n_q, dev, bn);
+        launch_merge(dk, dc, n_q, n_lists, k, k, ok.d, nullptr, nullptr, on.d, DECODE_NONE, s,
                      (flags & DI_F_LISTS_MAJOR) != 0);
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_key, dok, (size_t)n_q * k * 8, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_n, don, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
-        }
+        ok.copy_back(s);
+        on.copy_back(s);
         if (!(flags & DI_F_ASYNC) || !dev) DI_HIP(hipStreamSynchronize(s));
     });
 }

@@ -446,11 +446,8 @@ void pairwise_order_run(PairOrderWs &ws, Timer *timer, bool timing, const float 
     int32_t *d_ldoc = ws.ldoc.as<int32_t>();
     int64_t *d_lkey = ws.loff.as<int64_t>(), *d_lrun = d_lkey + (n_docs + 1),
             *d_ltile = d_lrun + (n_docs + 1);
-    int64_t *d_cu = out_cu;
-    if (!out_dev) {
-        ws.o_cu.reserve((size_t)(n_docs + 1) * 8);
-        d_cu = ws.o_cu.as<int64_t>();
-    }
+    StagedOut<int64_t> cu(out_cu, (size_t)n_docs + 1, out_dev, ws.o_cu);
+    int64_t *d_cu = cu.d;
     DI_HIP(hipMemsetAsync(d_err, 0, 4, s));
     {
         TimedLaunch tl(tm, timing, "pair_count", s);
@@ -464,11 +461,8 @@ void pairwise_order_run(PairOrderWs &ws, Timer *timer, bool timing, const float 
     int64_t info[PO_INFO];
     int32_t err = 0;
     DI_HIP(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, s));
-    DI_HIP(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
-    if (!out_dev)
-        DI_HIP(hipMemcpyAsync(out_cu, d_cu, (size_t)(n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-    DI_HIP(hipStreamSynchronize(s));
-    tm.resolve();
+    cu.copy_back(s);
+    read_back(err, d_err, s, &tm);
     DI_REQUIRE(!(err & ERR_CU), DI_EINVAL,
                "cu_terms / cu_pairs: every document needs T <= %d terms and T (T - 1) / 2 pairs, "
                "ending at n_terms and n_pairs", PO_MAX_T);
@@ -479,17 +473,12 @@ void pairwise_order_run(PairOrderWs &ws, Timer *timer, bool timing, const float 
                (long long)total, (long long)out_cap);
     if (total == 0) return;
     DI_REQUIRE(out_first && out_second && out_score, DI_EINVAL, "null output");
-    int32_t *d_first = out_first, *d_second = out_second;
-    float *d_score = out_score;
-    if (!out_dev) {
-        ws.o_first.reserve((size_t)total * 4);
-        ws.o_second.reserve((size_t)total * 4);
-        ws.o_score.reserve((size_t)total * 4);
-        d_first = ws.o_first.as<int32_t>();
-        d_second = ws.o_second.as<int32_t>();
-        d_score = ws.o_score.as<float>();
-        out_cap = total;
-    }
+    StagedOut<int32_t> first(out_first, (size_t)total, out_dev, ws.o_first),
+        second(out_second, (size_t)total, out_dev, ws.o_second);
+    StagedOut<float> score(out_score, (size_t)total, out_dev, ws.o_score);
+    int32_t *d_first = first.d, *d_second = second.d;
+    float *d_score = score.d;
+    if (!out_dev) out_cap = total;
     const int n_large = (int)info[PO_N_LARGE];
     const int rnd = round3 ? 1 : 0;
     uint64_t *kA = nullptr, *kB = nullptr;
@@ -544,11 +533,9 @@ void pairwise_order_run(PairOrderWs &ws, Timer *timer, bool timing, const float 
                            out_cap, d_first, d_second, d_score, d_err);
         check_launch("pair_emit");
     }
-    if (!out_dev) {
-        DI_HIP(hipMemcpyAsync(out_first, d_first, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        DI_HIP(hipMemcpyAsync(out_second, d_second, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        DI_HIP(hipMemcpyAsync(out_score, d_score, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-    }
+    first.copy_back(s);
+    second.copy_back(s);
+    score.copy_back(s);
     DI_HIP(hipStreamSynchronize(s));
     tm.resolve();
 }
@@ -566,34 +553,21 @@ extern "C" int di_pairwise_order(const float *single, const float *pair, const i
     return guard([&] {
         DI_REQUIRE(cu_terms && cu_pairs && out_cu && n_out && n_docs >= 0 && out_cap >= 0,
                    DI_EINVAL, "bad argument");
-        int count = 0;
-        DI_REQUIRE(hipGetDeviceCount(&count) == hipSuccess && count > 0, DI_ENODEV,
-                   "no HIP device");
-        DI_REQUIRE(device >= 0 && device < count, DI_EINVAL, "device %d of %d", device, count);
-        int prev = -1;
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != device) DI_HIP(hipSetDevice(device));
-        struct Restore {
-            int prev, dev;
-            ~Restore() {
-                if (prev != dev) (void)hipSetDevice(prev);
-            }
-        } restore{prev, device};
+        check_device(device);
+        DeviceScope ds(device);
         const bool dev = flags & DI_F_DEVICE_PTRS;
         hipStream_t s = (hipStream_t)hip_stream;
         if (!dev) {  // the checks of di_encode_pairwise, with the document in the message
-            DI_REQUIRE(cu_terms[0] == 0 && cu_pairs[0] == 0, DI_EINVAL,
-                       "cu_terms[0] and cu_pairs[0] must be 0");
+            DI_REQUIRE(cu_pairs[0] == 0, DI_EINVAL, "cu_pairs[0] must be 0");
+            n_terms = check_cu(cu_terms, n_docs, "cu_terms");
             for (int d = 0; d < n_docs; ++d) {
                 const int64_t T = (int64_t)cu_terms[d + 1] - cu_terms[d];
-                DI_REQUIRE(T >= 0, DI_EINVAL, "cu_terms not monotone at %d", d);
                 DI_REQUIRE(cu_pairs[d + 1] - cu_pairs[d] == T * (T - 1) / 2, DI_EINVAL,
                            "cu_pairs: document %d has %lld terms, so %lld pairs", d, (long long)T,
                            (long long)(T * (T - 1) / 2));
                 DI_REQUIRE(T <= PO_MAX_T, DI_ERANGE, "document %d has %lld terms > %d", d,
                            (long long)T, PO_MAX_T);
             }
-            n_terms = cu_terms[n_docs];
             n_pairs = cu_pairs[n_docs];
         }
         DI_REQUIRE(n_terms >= 0 && n_terms < (1ll << 31) && n_pairs >= 0, DI_EINVAL,
@@ -601,16 +575,12 @@ extern "C" int di_pairwise_order(const float *single, const float *pair, const i
         DI_REQUIRE((n_terms == 0 || single) && (n_pairs == 0 || pair), DI_EINVAL, "null input");
         PairOrderWs ws;
         DevBuf b_single, b_pair, b_ct, b_cp, b_sp;
-        const float *d_single =
-            (const float *)stage_in(single, (size_t)n_terms * 4, dev, b_single, s);
-        const float *d_pair = (const float *)stage_in(pair, (size_t)n_pairs * 4, dev, b_pair, s);
-        const int32_t *d_ct =
-            (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, b_ct, s);
-        const int64_t *d_cp =
-            (const int64_t *)stage_in(cu_pairs, (size_t)(n_docs + 1) * 8, dev, b_cp, s);
-        const int32_t *d_sp = single_pos
-            ? (const int32_t *)stage_in(single_pos, (size_t)n_terms * 4, dev, b_sp, s) : nullptr;
-        if (n_terms == 0) d_sp = nullptr;
+        const float *d_single = stage_in(single, (size_t)n_terms, dev, b_single, s);
+        const float *d_pair = stage_in(pair, (size_t)n_pairs, dev, b_pair, s);
+        const int32_t *d_ct = stage_in(cu_terms, (size_t)n_docs + 1, dev, b_ct, s);
+        const int64_t *d_cp = stage_in(cu_pairs, (size_t)n_docs + 1, dev, b_cp, s);
+        const int32_t *d_sp = single_pos && n_terms
+            ? stage_in(single_pos, (size_t)n_terms, dev, b_sp, s) : nullptr;
         pairwise_order_run(ws, nullptr, false, d_single, d_pair, d_ct, d_cp, d_sp, n_docs, n_terms,
                            n_pairs, out_cu, out_first, out_second, out_score, out_cap, n_out, dev,
                            flags & DI_F_ROUND3, s);

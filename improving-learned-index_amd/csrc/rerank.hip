@@ -159,25 +159,6 @@ rerank_score_kernel(const uint64_t *__restrict__ keys, const int64_t *__restrict
     }
 }
 
-struct DeviceScope {
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != dev) DI_HIP(hipSetDevice(dev));
-    }
-    ~DeviceScope() {
-        int cur;
-        if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int32_t read_i32(const int32_t *d_p, hipStream_t s) {
-    int32_t v = 0;
-    DI_HIP(hipMemcpyAsync(&v, d_p, 4, hipMemcpyDeviceToHost, s));
-    DI_HIP(hipStreamSynchronize(s));
-    return v;
-}
-
 }  // namespace
 }  // namespace di
 
@@ -204,14 +185,6 @@ void ts_reserve(di_term_store *ts, int64_t n_docs, int64_t n_terms, hipStream_t 
     grow_keep(ts->keys, (size_t)std::max<int64_t>(n_terms, 1) * 8, (size_t)ts->n_terms * 8, s);
 }
 
-int32_t read_errors(di_term_store *ts, hipStream_t s) {
-    int32_t h = 0;
-    DI_HIP(hipMemcpyAsync(&h, ts->err.p, 4, hipMemcpyDeviceToHost, s));
-    DI_HIP(hipStreamSynchronize(s));
-    ts->timer.resolve();
-    return h;
-}
-
 }  // namespace
 
 extern "C" {
@@ -220,9 +193,7 @@ int di_term_store_create(int device, di_term_store **out) {
     return guard([&] {
         DI_REQUIRE(out, DI_EINVAL, "null output");
         *out = nullptr;
-        int ndev = 0;
-        DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV, "no HIP device");
-        DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
+        check_device(device);
         DeviceScope ds(device);
         di_term_store *ts = new di_term_store;
         ts->device = device;
@@ -259,31 +230,15 @@ int di_term_store_append(di_term_store *ts, const uint32_t *term_ids, const floa
         // the offsets are checked on the host before anything changes (with device
         // pointers a copy of them is read back: 4 bytes a passage)
         std::vector<int32_t> h_cu;
-        const int32_t *cu = cu_terms;
-        if (dev) {
-            h_cu.resize((size_t)n_docs + 1);
-            DI_HIP(hipMemcpyAsync(h_cu.data(), cu_terms, h_cu.size() * 4, hipMemcpyDeviceToHost,
-                                  s));
-            DI_HIP(hipStreamSynchronize(s));
-            cu = h_cu.data();
-        }
-        DI_REQUIRE(cu[0] == 0, DI_EINVAL, "cu_terms[0] must be 0");
-        for (int d = 0; d < n_docs; ++d) {
-            const int64_t T = (int64_t)cu[d + 1] - cu[d];
-            DI_REQUIRE(T >= 0, DI_EINVAL, "cu_terms not monotone at %d", d);
-            DI_REQUIRE(T <= TS_MAX_T, DI_ERANGE, "passage %d has %lld terms > %d", d,
-                       (long long)T, TS_MAX_T);
-        }
-        const int64_t total = cu[n_docs];
+        const int64_t total =
+            check_cu(host_cu(cu_terms, n_docs, dev, h_cu, s), n_docs, "cu_terms", TS_MAX_T);
         DI_REQUIRE(total == 0 || (term_ids && impacts), DI_EINVAL, "null input");
         DI_REQUIRE(ts->n_docs + n_docs < (1ll << 31), DI_ERANGE,
                    "a store holds fewer than 2^31 passages");
         ts_reserve(ts, ts->n_docs + n_docs, ts->n_terms + total, s);
-        const uint32_t *d_ids =
-            (const uint32_t *)stage_in(term_ids, (size_t)total * 4, dev, ts->in_ids, s);
-        const float *d_imp = (const float *)stage_in(impacts, (size_t)total * 4, dev, ts->in_imp, s);
-        const int32_t *d_cu =
-            (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, ts->in_cu, s);
+        const uint32_t *d_ids = stage_in(term_ids, (size_t)total, dev, ts->in_ids, s);
+        const float *d_imp = stage_in(impacts, (size_t)total, dev, ts->in_imp, s);
+        const int32_t *d_cu = stage_in(cu_terms, (size_t)n_docs + 1, dev, ts->in_cu, s);
         DI_HIP(hipMemsetAsync(ts->err.p, 0, 4, s));
         {
             TimedLaunch tl(ts->timer, timing, "ts_sort", s);
@@ -293,7 +248,8 @@ int di_term_store_append(di_term_store *ts, const uint32_t *term_ids, const floa
                                ts->err.as<int32_t>());
             check_launch("rerank_sort");
         }
-        const int32_t e = read_errors(ts, s);
+        int32_t e = 0;
+        read_back(e, ts->err.p, s, &ts->timer);
         DI_REQUIRE(!(e & TS_ERR_CU), DI_EINVAL, "cu_terms must start at 0 and not decrease");
         DI_REQUIRE(!(e & TS_ERR_LONG), DI_ERANGE, "a passage has more than %d terms", TS_MAX_T);
         DI_REQUIRE(!(e & TS_ERR_DUP), DI_EINVAL, "a passage holds the same term id twice");
@@ -323,54 +279,37 @@ int di_term_store_score(di_term_store *ts, const uint32_t *q_terms, const int32_
         if (n_q == 0) return;
         int64_t n_c = 0, n_qt = 0;
         if (!dev) {
-            DI_REQUIRE(cu_q[0] == 0 && cu_cand[0] == 0, DI_EINVAL,
-                       "cu_q[0] and cu_cand[0] must be 0");
-            for (int q = 0; q < n_q; ++q) {
-                const int64_t Q = (int64_t)cu_q[q + 1] - cu_q[q];
-                DI_REQUIRE(Q >= 0 && cu_cand[q + 1] >= cu_cand[q], DI_EINVAL,
-                           "cu_q / cu_cand not monotone at %d", q);
-                DI_REQUIRE(Q <= DI_MAX_QUERY_TERMS, DI_ERANGE, "query %d has %lld terms > %d", q,
-                           (long long)Q, DI_MAX_QUERY_TERMS);
-            }
-            n_c = cu_cand[n_q];
-            n_qt = cu_q[n_q];
+            n_c = check_cu(cu_cand, n_q, "cu_cand");
+            n_qt = check_cu(cu_q, n_q, "cu_q", DI_MAX_QUERY_TERMS);
         } else {
-            n_c = read_i32(cu_cand + n_q, s);
+            int32_t last = 0;
+            read_back(last, cu_cand + n_q, s);
+            n_c = last;
             DI_REQUIRE(n_c >= 0, DI_EINVAL, "cu_cand ends at %lld", (long long)n_c);
         }
         if (n_c == 0) return;
         DI_REQUIRE(cand_doc && out_score && out_match && (n_qt == 0 || q_terms), DI_EINVAL,
                    "null argument");
-        const uint32_t *d_q = (const uint32_t *)stage_in(q_terms, (size_t)n_qt * 4, dev, ts->in_q, s);
-        const int32_t *d_cq =
-            (const int32_t *)stage_in(cu_q, (size_t)(n_q + 1) * 4, dev, ts->in_cq, s);
-        const int32_t *d_cand =
-            (const int32_t *)stage_in(cand_doc, (size_t)n_c * 4, dev, ts->in_cand, s);
-        const int32_t *d_cc =
-            (const int32_t *)stage_in(cu_cand, (size_t)(n_q + 1) * 4, dev, ts->in_cc, s);
-        float *d_score = out_score;
-        int32_t *d_match = out_match;
-        if (!dev) {
-            ts->o_score.reserve((size_t)n_c * 4);
-            ts->o_match.reserve((size_t)n_c * 4);
-            d_score = ts->o_score.as<float>();
-            d_match = ts->o_match.as<int32_t>();
-        }
+        const uint32_t *d_q = stage_in(q_terms, (size_t)n_qt, dev, ts->in_q, s);
+        const int32_t *d_cq = stage_in(cu_q, (size_t)n_q + 1, dev, ts->in_cq, s);
+        const int32_t *d_cand = stage_in(cand_doc, (size_t)n_c, dev, ts->in_cand, s);
+        const int32_t *d_cc = stage_in(cu_cand, (size_t)n_q + 1, dev, ts->in_cc, s);
+        StagedOut<float> score(out_score, (size_t)n_c, dev, ts->o_score);
+        StagedOut<int32_t> match(out_match, (size_t)n_c, dev, ts->o_match);
         DI_HIP(hipMemsetAsync(ts->err.p, 0, 4, s));
         {
             TimedLaunch tl(ts->timer, timing, "ts_score", s);
             const int64_t blocks = (n_c + TS_WAVES - 1) / TS_WAVES;
             hipLaunchKernelGGL(rerank_score_kernel, dim3((unsigned)blocks), dim3(TS_SCORE_THREADS),
                                0, s, ts->keys.as<uint64_t>(), ts->off.as<int64_t>(), ts->n_docs,
-                               d_q, d_cq, n_q, d_cand, d_cc, n_c, d_score, d_match,
+                               d_q, d_cq, n_q, d_cand, d_cc, n_c, score.d, match.d,
                                ts->err.as<int32_t>());
             check_launch("rerank_score");
         }
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_score, d_score, (size_t)n_c * 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_match, d_match, (size_t)n_c * 4, hipMemcpyDeviceToHost, s));
-        }
-        const int32_t e = read_errors(ts, s);
+        score.copy_back(s);
+        match.copy_back(s);
+        int32_t e = 0;
+        read_back(e, ts->err.p, s, &ts->timer);
         DI_REQUIRE(!(e & TS_ERR_CAND), DI_EINVAL,
                    "a candidate index is outside the store's %lld passages",
                    (long long)ts->n_docs);

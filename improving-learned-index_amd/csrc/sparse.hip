@@ -438,10 +438,8 @@ int di_sparse_create(const int64_t *term_off, int64_t n_terms, const uint32_t *p
         DI_REQUIRE(out && term_off && n_terms >= 0, DI_EINVAL, "bad argument");
         DI_REQUIRE(n_docs <= DI_MAX_SPARSE_DOCS, DI_ERANGE, "%u docs > %u", n_docs,
                    DI_MAX_SPARSE_DOCS);
-        int ndev = 0;
-        DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV,
-                   "no HIP device");
-        DevScope ds(device);
+        check_device(device);
+        DeviceScope ds(device);
         std::unique_ptr<di_sparse> sp(new di_sparse());
         sparse_init(*sp, device);
         const int nb = (int)((n_docs + SP_DOCS - 1) / SP_DOCS);
@@ -511,7 +509,7 @@ int di_sparse_search(di_sparse *sp, const uint32_t *q_terms, const int32_t *cu_q
                    "bad argument");
         DI_REQUIRE(k > 0 && k <= DI_MAX_TOPK, DI_ERANGE, "k=%d outside [1, %d]", k,
                    DI_MAX_TOPK);
-        DevScope ds(sp->device);
+        DeviceScope ds(sp->device);
         const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
         hipStream_t s = sp->stream;
         if (n_q == 0) return;
@@ -532,25 +530,13 @@ int di_sparse_search(di_sparse *sp, const uint32_t *q_terms, const int32_t *cu_q
         const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(n_q, (1ll << 30) / per_q));
         sp->ws_ck.reserve((size_t)chunk * per_q);
         sp->ws_cn.reserve((size_t)chunk * nb * 4);
-        const uint32_t *dq = (const uint32_t *)stage_in(q_terms, (size_t)ntot * 4, dev,
-                                                        sp->ws_q, s);
-        const int32_t *dcu =
-            (const int32_t *)stage_in(cu_q, (size_t)(n_q + 1) * 4, dev, sp->ws_cu, s);
-        uint32_t *ddoc = out_doc, *dsc = reinterpret_cast<uint32_t *>(out_score);
-        int32_t *dn = out_n;
-        uint64_t *dkey = out_key;
-        if (!dev) {
-            sp->ws_doc.reserve((size_t)n_q * k * 4);
-            sp->ws_score.reserve((size_t)n_q * k * 4);
-            sp->ws_n.reserve((size_t)n_q * 4);
-            ddoc = sp->ws_doc.as<uint32_t>();
-            dsc = sp->ws_score.as<uint32_t>();
-            dn = sp->ws_n.as<int32_t>();
-            if (out_key) {
-                sp->ws_key.reserve((size_t)n_q * k * 8);
-                dkey = sp->ws_key.as<uint64_t>();
-            }
-        }
+        const uint32_t *dq = stage_in(q_terms, (size_t)ntot, dev, sp->ws_q, s);
+        const int32_t *dcu = stage_in(cu_q, (size_t)n_q + 1, dev, sp->ws_cu, s);
+        const size_t nk = (size_t)n_q * k;
+        StagedOut<uint32_t> doc(out_doc, nk, dev, sp->ws_doc),
+            sc(reinterpret_cast<uint32_t *>(out_score), nk, dev, sp->ws_score);
+        StagedOut<int32_t> on(out_n, (size_t)n_q, dev, sp->ws_n);
+        StagedOut<uint64_t> key(out_key, nk, dev, sp->ws_key);
         for (int q0 = 0; q0 < n_q; q0 += chunk) {
             const int nq = std::min(chunk, n_q - q0);
             if (sp->nb == 0) {
@@ -567,17 +553,13 @@ int di_sparse_search(di_sparse *sp, const uint32_t *q_terms, const int32_t *cu_q
             }
             TimedLaunch tl(sp->timer, timing, "merge_topk", s);
             launch_merge(sp->ws_ck.as<uint64_t>(), sp->ws_cn.as<int32_t>(), nq, nb, k, k,
-                         dkey ? dkey + (int64_t)q0 * k : nullptr, ddoc + (int64_t)q0 * k,
-                         dsc + (int64_t)q0 * k, dn + q0, 1 /*DECODE_SPARSE*/, s, false, nullptr);
+                         key.d ? key.d + (int64_t)q0 * k : nullptr, doc.d + (int64_t)q0 * k,
+                         sc.d + (int64_t)q0 * k, on.d + q0, 1 /*DECODE_SPARSE*/, s, false, nullptr);
         }
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_doc, ddoc, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_score, dsc, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_n, dn, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
-            if (out_key)
-                DI_HIP(hipMemcpyAsync(out_key, dkey, (size_t)n_q * k * 8, hipMemcpyDeviceToHost,
-                                      s));
-        }
+        doc.copy_back(s);
+        sc.copy_back(s);
+        on.copy_back(s);
+        key.copy_back(s);
         if (!(flags & DI_F_ASYNC) || !dev) {
             DI_HIP(hipStreamSynchronize(s));
             sp->timer.resolve();
@@ -596,7 +578,7 @@ int di_sparse_search_f64(di_sparse *sp, const uint32_t *q_terms, const int32_t *
                    "bad argument");
         DI_REQUIRE(k > 0 && k <= DI_MAX_TOPK, DI_ERANGE, "k=%d outside [1, %d]", k,
                    DI_MAX_TOPK);
-        DevScope ds(sp->device);
+        DeviceScope ds(sp->device);
         const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
         hipStream_t s = sp->stream;
         if (n_q == 0) return;
@@ -617,21 +599,11 @@ int di_sparse_search_f64(di_sparse *sp, const uint32_t *q_terms, const int32_t *
         const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(n_q, (1ll << 30) / per_q));
         sp->ws_ck.reserve((size_t)chunk * per_q);
         sp->ws_cn.reserve((size_t)chunk * nl * 4);
-        const uint32_t *dq = (const uint32_t *)stage_in(q_terms, (size_t)ntot * 4, dev,
-                                                        sp->ws_q, s);
-        const int32_t *dcu =
-            (const int32_t *)stage_in(cu_q, (size_t)(n_q + 1) * 4, dev, sp->ws_cu, s);
-        uint32_t *ddoc = out_doc;
-        double *dsc = out_score;
-        int32_t *dn = out_n;
-        if (!dev) {
-            sp->ws_doc.reserve((size_t)n_q * k * 4);
-            sp->ws_score.reserve((size_t)n_q * k * 8);
-            sp->ws_n.reserve((size_t)n_q * 4);
-            ddoc = sp->ws_doc.as<uint32_t>();
-            dsc = sp->ws_score.as<double>();
-            dn = sp->ws_n.as<int32_t>();
-        }
+        const uint32_t *dq = stage_in(q_terms, (size_t)ntot, dev, sp->ws_q, s);
+        const int32_t *dcu = stage_in(cu_q, (size_t)n_q + 1, dev, sp->ws_cu, s);
+        StagedOut<uint32_t> doc(out_doc, (size_t)n_q * k, dev, sp->ws_doc);
+        StagedOut<double> sc(out_score, (size_t)n_q * k, dev, sp->ws_score);
+        StagedOut<int32_t> on(out_n, (size_t)n_q, dev, sp->ws_n);
         for (int q0 = 0; q0 < n_q; q0 += chunk) {
             const int nq = std::min(chunk, n_q - q0);
             Key96 *ck = sp->ws_ck.as<Key96>();
@@ -649,14 +621,12 @@ int di_sparse_search_f64(di_sparse *sp, const uint32_t *q_terms, const int32_t *
             TimedLaunch tl(sp->timer, timing, "sparse_merge64", s);
             hipLaunchKernelGGL(sparse_merge64_kernel, dim3(nq), dim3(SP_THREADS),
                                sizeof(Merge64Shared), s, ck, sp->ws_cn.as<int32_t>(), nl, k,
-                               ddoc + (int64_t)q0 * k, dsc + (int64_t)q0 * k, dn + q0);
+                               doc.d + (int64_t)q0 * k, sc.d + (int64_t)q0 * k, on.d + q0);
             check_launch("sparse_merge64");
         }
-        if (!dev) {
-            DI_HIP(hipMemcpyAsync(out_doc, ddoc, (size_t)n_q * k * 4, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_score, dsc, (size_t)n_q * k * 8, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipMemcpyAsync(out_n, dn, (size_t)n_q * 4, hipMemcpyDeviceToHost, s));
-        }
+        doc.copy_back(s);
+        sc.copy_back(s);
+        on.copy_back(s);
         if (!(flags & DI_F_ASYNC) || !dev) {
             DI_HIP(hipStreamSynchronize(s));
             sp->timer.resolve();
@@ -689,7 +659,7 @@ int di_sparse_destroy(di_sparse *sp) {
     return guard([&] {
         if (!sp) return;
         {
-            DevScope ds(sp->device);
+            DeviceScope ds(sp->device);
             if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
         }
         delete sp;

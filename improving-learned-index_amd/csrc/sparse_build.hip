@@ -332,10 +332,8 @@ int di_sparse_builder_create(int device, di_sparse_builder **out) {
     return guard([&] {
         DI_REQUIRE(out, DI_EINVAL, "null output");
         *out = nullptr;
-        int ndev = 0;
-        DI_REQUIRE(hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0, DI_ENODEV, "no HIP device");
-        DI_REQUIRE(device >= 0 && device < ndev, DI_EINVAL, "bad device %d", device);
-        DevScope ds(device);
+        check_device(device);
+        DeviceScope ds(device);
         std::unique_ptr<di_sparse_builder> b(new di_sparse_builder);
         b->device = device;
         b->kept.reserve(8);
@@ -349,7 +347,7 @@ int di_sparse_builder_reserve(di_sparse_builder *b, int64_t n_docs, int64_t n_pa
         DI_REQUIRE(b && n_docs >= 0 && n_pairs >= 0, DI_EINVAL, "bad argument");
         DI_REQUIRE(n_docs <= (int64_t)DI_MAX_SPARSE_DOCS, DI_ERANGE, "%lld docs > %u",
                    (long long)n_docs, DI_MAX_SPARSE_DOCS);
-        DevScope ds(b->device);
+        DeviceScope ds(b->device);
         sb_reserve(b, std::max(n_pairs, b->n_pairs), nullptr);
     });
 }
@@ -361,7 +359,7 @@ int di_sparse_builder_append(di_sparse_builder *b, const uint32_t *term_ids,
         DI_REQUIRE(b && cu_terms && first_doc && n_docs >= 0, DI_EINVAL, "bad argument");
         DI_REQUIRE(b->n_docs + n_docs <= (int64_t)DI_MAX_SPARSE_DOCS, DI_ERANGE,
                    "%lld docs > %u", (long long)(b->n_docs + n_docs), DI_MAX_SPARSE_DOCS);
-        DevScope ds(b->device);
+        DeviceScope ds(b->device);
         const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
         hipStream_t s = (hipStream_t)hip_stream;
         *first_doc = b->n_docs;
@@ -369,27 +367,13 @@ int di_sparse_builder_append(di_sparse_builder *b, const uint32_t *term_ids,
         // the offsets are checked on the host before anything changes (with device
         // pointers a copy of them is read back: 4 bytes a document)
         std::vector<int32_t> h_cu;
-        const int32_t *cu = cu_terms;
-        if (dev) {
-            h_cu.resize((size_t)n_docs + 1);
-            DI_HIP(hipMemcpyAsync(h_cu.data(), cu_terms, h_cu.size() * 4, hipMemcpyDeviceToHost,
-                                  s));
-            DI_HIP(hipStreamSynchronize(s));
-            cu = h_cu.data();
-        }
-        DI_REQUIRE(cu[0] == 0, DI_EINVAL, "cu_terms[0] must be 0");
-        for (int d = 0; d < n_docs; ++d)
-            DI_REQUIRE(cu[d + 1] >= cu[d], DI_EINVAL, "cu_terms not monotone at %d", d);
-        const int64_t total = cu[n_docs];
+        const int64_t total = check_cu(host_cu(cu_terms, n_docs, dev, h_cu, s), n_docs, "cu_terms");
         DI_REQUIRE(total == 0 || (term_ids && impacts), DI_EINVAL, "null input");
         if (total > 0) {
             sb_reserve(b, b->n_pairs + total, s);
-            const uint32_t *d_ids =
-                (const uint32_t *)stage_in(term_ids, (size_t)total * 4, dev, b->in_ids, s);
-            const float *d_imp =
-                (const float *)stage_in(impacts, (size_t)total * 4, dev, b->in_imp, s);
-            const int32_t *d_cu =
-                (const int32_t *)stage_in(cu_terms, (size_t)(n_docs + 1) * 4, dev, b->in_cu, s);
+            const uint32_t *d_ids = stage_in(term_ids, (size_t)total, dev, b->in_ids, s);
+            const float *d_imp = stage_in(impacts, (size_t)total, dev, b->in_imp, s);
+            const int32_t *d_cu = stage_in(cu_terms, (size_t)n_docs + 1, dev, b->in_cu, s);
             DI_HIP(hipMemsetAsync(b->kept.p, 0, 8, s));
             {
                 TimedLaunch tl(b->timer, timing, "sb_append", s);
@@ -401,9 +385,7 @@ int di_sparse_builder_append(di_sparse_builder *b, const uint32_t *term_ids,
                 check_launch("sb_append");
             }
             unsigned long long kept = 0;
-            DI_HIP(hipMemcpyAsync(&kept, b->kept.p, 8, hipMemcpyDeviceToHost, s));
-            DI_HIP(hipStreamSynchronize(s));
-            b->timer.resolve();
+            read_back(kept, b->kept.p, s, &b->timer);
             DI_REQUIRE((int64_t)kept <= total, DI_EHIP, "sb_append kept %llu of %lld pairs", kept,
                        (long long)total);
             b->n_pairs += (int64_t)kept;
@@ -426,7 +408,7 @@ int di_sparse_builder_finish(di_sparse_builder *b, int64_t n_terms, void *hip_st
         DI_REQUIRE(b && out && n_terms >= 0, DI_EINVAL, "bad argument");
         *out = nullptr;
         DI_REQUIRE(n_terms <= (int64_t)UINT32_MAX, DI_ERANGE, "term ids are 32-bit");
-        DevScope ds(b->device);
+        DeviceScope ds(b->device);
         const bool timing = flags & DI_F_TIMING;
         hipStream_t s = (hipStream_t)hip_stream;
         const int64_t n = b->n_pairs;
@@ -506,9 +488,7 @@ int di_sparse_builder_finish(di_sparse_builder *b, int64_t n_terms, void *hip_st
             check_launch("sb_order_long");
         }
         Ctrl h{};
-        DI_HIP(hipMemcpyAsync(&h, ctrl.p, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
-        DI_HIP(hipStreamSynchronize(s));
-        sp->timer.resolve();
+        read_back(h, ctrl.p, s, &sp->timer);
         DI_REQUIRE(!(h.err & SB_ERR_TERM), DI_EINVAL, "a term id is not below n_terms = %lld",
                    (long long)n_terms);
         DI_REQUIRE(!(h.err & SB_ERR_DUP), DI_EINVAL, "a document holds the same term id twice");
@@ -525,7 +505,7 @@ int di_sparse_builder_finish(di_sparse_builder *b, int64_t n_terms, void *hip_st
 int di_sparse_builder_destroy(di_sparse_builder *b) {
     return guard([&] {
         if (!b) return;
-        DevScope ds(b->device);
+        DeviceScope ds(b->device);
         delete b;
     });
 }
@@ -534,7 +514,7 @@ int di_sparse_export(const di_sparse *sp, int64_t *term_start, uint32_t *blk_off
                      float *pimp) {
     return guard([&] {
         DI_REQUIRE(sp, DI_EINVAL, "null handle");
-        DevScope ds(sp->device);
+        DeviceScope ds(sp->device);
         DI_HIP(hipStreamSynchronize(sp->stream));
         const size_t cells = (size_t)sp->n_terms * (size_t)(sp->nb + 1);
         if (term_start && sp->n_terms)

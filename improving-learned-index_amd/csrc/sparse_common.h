@@ -22,18 +22,6 @@ struct di_sparse {
 
 namespace di {
 
-struct DevScope {
-    int prev = -1;
-    explicit DevScope(int d) {
-        DI_HIP(hipGetDevice(&prev));
-        if (prev != d) DI_HIP(hipSetDevice(d));
-    }
-    ~DevScope() {
-        int c;
-        if (hipGetDevice(&c) == hipSuccess && c != prev) (void)hipSetDevice(prev);
-    }
-};
-
 // A fresh handle's device, stream and kernel attributes (the current device is `device`).
 void sparse_init(di_sparse &sp, int device);
 

@@ -263,21 +263,20 @@ extern "C" int di_quantize_file(const char *input_path, const char *output_path,
                 std::vector<double>().swap(v);
             }
         });
-        int prev = 0;
-        DI_HIP(hipGetDevice(&prev));
-        DI_HIP(hipSetDevice(device));
-        DevBuf dv, dq, dm;
-        dv.reserve((size_t)std::max<int64_t>(n, 1) * 8);
-        dq.reserve((size_t)std::max<int64_t>(n, 1) * 4);
-        dm.reserve(16);
-        if (n) DI_HIP(hipMemcpy(dv.p, vals.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-        launch_quantize_f64(dv.as<double>(), n, max_val, bits, dq.as<int32_t>(),
-                            dm.as<unsigned long long>(), nullptr);
         std::vector<int32_t> q((size_t)std::max<int64_t>(n, 1));
         unsigned long long mb = 0;
-        if (n) DI_HIP(hipMemcpy(q.data(), dq.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        DI_HIP(hipMemcpy(&mb, dm.p, 8, hipMemcpyDeviceToHost));
-        (void)hipSetDevice(prev);
+        {
+            DeviceScope ds(device);
+            DevBuf dv, dq, dm;
+            dv.reserve((size_t)std::max<int64_t>(n, 1) * 8);
+            dq.reserve((size_t)std::max<int64_t>(n, 1) * 4);
+            dm.reserve(16);
+            if (n) DI_HIP(hipMemcpy(dv.p, vals.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+            launch_quantize_f64(dv.as<double>(), n, max_val, bits, dq.as<int32_t>(),
+                                dm.as<unsigned long long>(), nullptr);
+            if (n) DI_HIP(hipMemcpy(q.data(), dq.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+            DI_HIP(hipMemcpy(&mb, dm.p, 8, hipMemcpyDeviceToHost));
+        }
         double m;
         std::memcpy(&m, &mb, 8);
         if (!output_path) {  // max only (find_max_value, quantize.py:17-24; 0 if no term)
