@@ -29,6 +29,8 @@ DI_TERM_STORE_MAX_TERMS = 2048  # pairs of one passage of a TermStore (include/d
 DI_F_ROUND3 = 0x10
 DI_ERANGE = -4
 DI_EINVAL = -1
+DI_EFORMAT = -7
+DI_INDEX_BUILD_TILE = 4096  # postings one workgroup of the index builder's sort places
 DI_MAX_SPARSE_DOCS = 16777215  # documents of a float index (include/deepimpact.h)
 SPARSE_BLOCK_DOCS = 16384  # documents of one block of the float index's layout
 
@@ -144,6 +146,21 @@ SIGNATURES = {
     "di_sparse_builder_finish": (ctypes.c_int, [P, I64, P, U32, P]),
     "di_sparse_builder_destroy": (ctypes.c_int, [P]),
     "di_sparse_export": (ctypes.c_int, [P, P, P, P, P]),
+    "di_term_table_create": (ctypes.c_int, [P]),
+    "di_term_table_intern": (ctypes.c_int, [P, P, P, I64, P]),
+    "di_term_table_info": (ctypes.c_int, [P, P, P]),
+    "di_term_table_export": (ctypes.c_int, [P, P, P]),
+    "di_term_table_rows": (ctypes.c_int, [P, P, P, P]),
+    "di_term_table_destroy": (ctypes.c_int, [P]),
+    "di_index_builder_create": (ctypes.c_int, [ctypes.c_int, P]),
+    "di_index_builder_reserve": (ctypes.c_int, [P, I64, I64]),
+    "di_index_builder_append": (ctypes.c_int, [P, P, P, P, I32, P, P, U32]),
+    "di_index_builder_info": (ctypes.c_int, [P, P, P]),
+    "di_index_builder_quantize": (ctypes.c_int, [P, I64, ctypes.c_double, P, U32, P, P, P]),
+    "di_index_builder_postings": (ctypes.c_int, [P, P, I64, P, U32, P, P, P]),
+    "di_index_builder_timing": (ctypes.c_int, [P, ctypes.c_char_p, P, ctypes.c_int]),
+    "di_index_builder_destroy": (ctypes.c_int, [P]),
+    "di_write_reference_index": (ctypes.c_int, [ctypes.c_char_p, P, P, I64, P, P, P]),
     "di_synth_postings": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P, P, I64,
                                          P, P]),
     "di_synth_postings_skewed": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P,
@@ -840,3 +857,163 @@ class SparseBuilder(_Handle):
         check(lib().di_sparse_builder_finish(self._h, int(n_terms), ctypes.c_void_p(stream or 0),
                                              DI_F_TIMING if timing else 0, ctypes.byref(h)))
         return DeviceSparseIndex._from_handle(h)
+
+
+class TermTable(_Handle):
+    """Term strings numbered in order of first appearance (di_term_table_*): the host side
+    of IndexBuilder.  Terms go in as the tokenizer workers' packed form -- one UTF-8 blob
+    and byte offsets -- so no Python str is made per term."""
+
+    _family = "di_term_table"
+
+    def __init__(self):
+        h = ctypes.c_void_p()
+        check(lib().di_term_table_create(ctypes.byref(h)))
+        self._h = h
+
+    def intern(self, blob: bytes, term_off) -> np.ndarray:
+        """uint32 ids of the terms blob[term_off[i]:term_off[i + 1]]; a term the impact TSV
+        would not parse back to (empty, whitespace at an end, ', ' or ': ' inside) raises
+        DIError DI_EFORMAT and leaves the table as it was."""
+        term_off = np.ascontiguousarray(term_off, np.int64)
+        n = len(term_off) - 1
+        ids = np.zeros(max(n, 1), np.uint32)
+        if n > 0 and int(term_off[-1]) > len(blob):
+            raise ValueError("term_off names more bytes than the blob holds")
+        check(lib().di_term_table_intern(self._h, blob, ptr(term_off), n, ptr(ids)))
+        return ids[:max(n, 0)]
+
+    def intern_terms(self, terms) -> np.ndarray:
+        enc = [t.encode("utf-8") for t in terms]
+        off = np.zeros(len(enc) + 1, np.int64)
+        if enc:
+            off[1:] = np.cumsum([len(b) for b in enc])
+        return self.intern(b"".join(enc), off)
+
+    def __len__(self):
+        n = I64(0)
+        check(lib().di_term_table_info(self._h, ctypes.byref(n), None))
+        return n.value
+
+    def export(self):
+        """(blob, term_off int64 [n_terms + 1]): every term in id order."""
+        n, nb = I64(0), I64(0)
+        check(lib().di_term_table_info(self._h, ctypes.byref(n), ctypes.byref(nb)))
+        blob = ctypes.create_string_buffer(max(1, nb.value))
+        off = np.zeros(n.value + 1, np.int64)
+        check(lib().di_term_table_export(self._h, blob, ptr(off)))
+        return blob.raw[:nb.value], off
+
+    def rows(self, term_count):
+        """(term_row int32 [n_terms], n_rows): the terms with term_count > 0 numbered in
+        sorted() order of their strings -- the lines of vocab.txt -- every other term -1."""
+        term_count = np.ascontiguousarray(term_count, np.int64)
+        if term_count.size != len(self):
+            raise ValueError("term_count: one entry per term of the table")
+        row = np.full(max(term_count.size, 1), -1, np.int32)
+        n = I64(0)
+        check(lib().di_term_table_rows(self._h, ptr(term_count if term_count.size else
+                                                    np.zeros(1, np.int64)), ptr(row),
+                                       ctypes.byref(n)))
+        return row[:term_count.size], n.value
+
+    def vocab(self, term_row) -> dict:
+        """{term: row} of the terms that have a row (InvertedIndex.vocab)."""
+        blob, off = self.export()
+        ol = off.tolist()
+        return {blob[ol[i]:ol[i + 1]].decode("utf-8"): r
+                for i, r in enumerate(np.asarray(term_row).tolist()) if r >= 0}
+
+
+class IndexBuilder(_TimedHandle):
+    """Device builder of the quantized inverted index (di_index_builder_*): documents
+    appended as (term id, round3 impact) pairs -- host arrays, or the device buffers of an
+    encode step -- quantized, and returned as the postings di_index_create takes, in the
+    order of the reference's files."""
+
+    _family = "di_index_builder"
+
+    def __init__(self, device=0, n_docs=0, n_pairs=0):
+        h = ctypes.c_void_p()
+        check(lib().di_index_builder_create(device, ctypes.byref(h)))
+        self._h = h
+        self.device = device
+        self.n_kept, self.term_count = None, None  # of the last quantize
+        if n_docs or n_pairs:
+            self.reserve(n_docs, n_pairs)
+
+    def reserve(self, n_docs, n_pairs):
+        check(lib().di_index_builder_reserve(self._h, int(n_docs), int(n_pairs)))
+
+    def append(self, term_ids, impacts, cu_terms, stream=0, timing=False):
+        """Appends len(cu_terms) - 1 documents; document d holds (term_ids[i], impacts[i])
+        for i in [cu_terms[d], cu_terms[d + 1]), every pair kept.  Host numpy arrays, or
+        torch device tensors (all three; term ids as int32 bit patterns).  Returns the doc
+        id of the first appended document."""
+        term_ids, impacts, cu_terms, n_docs, flags = _append_arrays(term_ids, impacts, cu_terms,
+                                                                    timing)
+        first = I64(0)
+        check(lib().di_index_builder_append(self._h, ptr(term_ids), ptr(impacts), ptr(cu_terms),
+                                            n_docs, ctypes.byref(first),
+                                            ctypes.c_void_p(stream or 0), flags))
+        if n_docs > 0:
+            self.n_kept, self.term_count = None, None
+        return first.value
+
+    def info(self):
+        nd, npairs = I64(), I64()
+        check(lib().di_index_builder_info(self._h, ctypes.byref(nd), ctypes.byref(npairs)))
+        return {"n_docs": nd.value, "n_pairs": npairs.value}
+
+    def quantize(self, n_terms, max_val=None, stream=0, timing=False):
+        """quantize.py:13-47 on everything appended -> (max_used, term_count int64
+        [n_terms], n_kept).  max_val None: the maximum over all pairs."""
+        tc = np.zeros(max(int(n_terms), 1), np.int64)
+        used, kept = ctypes.c_double(0.0), I64(0)
+        check(lib().di_index_builder_quantize(
+            self._h, int(n_terms), float(max_val) if max_val is not None else -1.0,
+            ctypes.c_void_p(stream or 0), DI_F_TIMING if timing else 0, ctypes.byref(used),
+            ptr(tc), ctypes.byref(kept)))
+        self.n_kept, self.term_count = kept.value, tc[:int(n_terms)]
+        return used.value, self.term_count, kept.value
+
+    def postings(self, term_row, n_rows, stream=0, timing=False, device=False):
+        """The kept postings in the reference file order -> (term_off int64 [n_rows + 1],
+        pdoc uint32 [n_kept], pval uint8 [n_kept]): numpy arrays, or torch tensors on the
+        builder's device (device=True)."""
+        term_row = np.ascontiguousarray(term_row, np.int32)
+        if self.n_kept is None:
+            raise ValueError("IndexBuilder.quantize comes first")
+        n = self.n_kept
+        flags = DI_F_TIMING if timing else 0
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            term_off = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+            pdoc = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            pval = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+            flags |= DI_F_DEVICE_PTRS
+        else:
+            term_off = np.zeros(n_rows + 1, np.int64)
+            pdoc = np.zeros(max(n, 1), np.uint32)
+            pval = np.zeros(max(n, 1), np.uint8)
+        check(lib().di_index_builder_postings(
+            self._h, ptr(term_row if term_row.size else np.zeros(1, np.int32)), int(n_rows),
+            ctypes.c_void_p(stream or 0), flags, ptr(term_off), ptr(pdoc), ptr(pval)))
+        return term_off, pdoc[:n], pval[:n]
+
+
+def write_reference_index(out_dir, table: TermTable, term_row, n_rows, term_off, pdoc, pval):
+    """di_write_reference_index: vocab.txt / inverted_index.idx / inverted_index.dat of
+    IndexBuilder.postings' host arrays, the bytes create_index writes."""
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    term_row = np.ascontiguousarray(term_row, np.int32)
+    term_off = np.ascontiguousarray(term_off, np.int64)
+    pdoc = np.ascontiguousarray(pdoc, np.uint32)
+    pval = np.ascontiguousarray(pval, np.uint8)
+    one = np.zeros(1, np.int32)
+    check(lib().di_write_reference_index(str(out_dir).encode("utf-8"), table._h,
+                                         ptr(term_row if term_row.size else one), int(n_rows),
+                                         ptr(term_off), ptr(pdoc if pdoc.size else one),
+                                         ptr(pval if pval.size else one)))

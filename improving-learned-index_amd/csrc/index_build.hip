@@ -1,0 +1,662 @@
+// index_build.hip -- the quantized inverted index (the CSR di_index_create takes, the
+// bytes of inverted_index.dat) assembled on the device from (term id, impact) pairs per
+// document, e.g. di_encode's DI_F_ROUND3 output buffer, gfx950.
+//
+// Replaces, for inputs that are already on the device, the text route
+//   quantize_file (reference src/deep_impact/indexing/quantize.py:13-47) and
+//   InvertedIndexCreator (src/deep_impact/inverted_index/create.py:12-55).
+// The builder keeps every appended pair as (term id, doc, impact), 12 bytes, in document
+// order: pair i of an append goes to end + i, its document found by a search of cu_terms.
+//   ib_max       max(0, impacts) and a flag for a non-finite impact
+//   ib_quantize  val = int(double(impact) * (255 / max)), quantize.py:37-45 in fp64 (the
+//                arithmetic of quantize_kernel, enc_misc.hip); kept iff val > 0; the kept
+//                pairs of every tile of IB_TILE pairs and of every term id are counted
+//                (counts only: the order of the atomic adds reaches no position)
+//   ib_scan      exclusive scan of the tile counts (three kernels, int64)
+//   ib_compact   the kept pairs, in order, as 16-byte records (doc, term id, 255 - val):
+//                a record's place is its tile's offset + the kept pairs before it in the
+//                tile (wave ballots, the waves' counts added in wave order)
+// The kept records are therefore still in ascending doc order, and the reference order --
+// per term row value descending, doc ascending (create.py:41, a stable sort of a
+// doc-ordered list) -- is a *stable* sort of them by (row, 255 - val).  It is built as a
+// least-significant-digit radix sort with 8-bit digits: one pass on 255 - val, then
+// ceil(bits(n_rows - 1) / 8) passes on the row.  Every pass:
+//   ib_hist      per tile of IB_TILE records a 256-bin digit histogram (LDS counters)
+//   ib_scan      one exclusive scan over (digit, tile)
+//   ib_scatter   a record goes to scan[digit][tile] + the records of that digit before it
+//                in the tile.  The tile is walked 256 records at a time; inside a wave the
+//                rank among equal digits comes from eight ballots, across the four waves
+//                and across the rounds from LDS counters added in wave and round order.
+// Why it is stable and run-to-run identical: every place is a sum of counts of records
+// that precede it in the input order; no atomic hands out a slot.  Work per kept posting
+// and pass: two 16-byte reads, one 16-byte store, eight ballots, two LDS accesses.
+// The first pass also replaces the term id by its row (term_row), so the records of
+// ib_compact stay as they are and postings can be asked for again.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+#include "di_common.h"
+#include "topk_common.h"
+
+namespace di {
+namespace {
+
+constexpr int IB_THREADS = 256, IB_WAVES = IB_THREADS / 64;
+constexpr int IB_TILE = DI_INDEX_BUILD_TILE, IB_ROUNDS = IB_TILE / IB_THREADS;
+constexpr int IB_MAX_GRID = 1 << 16;  // blocks of a grid-stride launch
+constexpr int IB_SCAN_ITEMS = 8, IB_SCAN_CHUNK = IB_THREADS * IB_SCAN_ITEMS;
+static_assert(IB_TILE % IB_THREADS == 0, "whole rounds");
+
+constexpr int IB_ERR_TERM = 1;       // a term id >= n_terms
+constexpr int IB_ERR_RANGE = 2;      // a value above 255
+constexpr int IB_ERR_NONFINITE = 4;  // a NaN or infinite impact
+
+struct Ctrl {
+    int32_t err;
+    uint32_t max_bits;
+};
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_append_kernel(const uint32_t *__restrict__ term_ids, const float *__restrict__ impacts,
+                 const int32_t *__restrict__ cu_terms, int n_docs, int64_t total, uint32_t doc0,
+                 int64_t base, int64_t cap, uint32_t *__restrict__ o_tid,
+                 uint32_t *__restrict__ o_doc, float *__restrict__ o_imp) {
+    for (int64_t i = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * IB_THREADS) {
+        int lo = 0, hi = n_docs;  // the last document with cu_terms[d] <= i
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (cu_terms[mid] <= i) lo = mid; else hi = mid;
+        }
+        const int64_t pos = base + i;
+        if (pos < cap) {  // (always: the buffers hold base + total pairs)
+            o_tid[pos] = term_ids[i];
+            o_doc[pos] = doc0 + (uint32_t)lo;
+            o_imp[pos] = impacts[i];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_max_kernel(const float *__restrict__ v, int64_t n, Ctrl *__restrict__ ctrl) {
+    float m = 0.f;  // find_max_value starts at 0 (quantize.py:17)
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * IB_THREADS) {
+        const float x = v[i];
+        bad |= !isfinite(x);
+        m = fmaxf(m, x);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    // non-negative floats order like their bit patterns (-0.0 -> 0)
+    if (lane_id() == 0 && m > 0.f) atomicMax(&ctrl->max_bits, __float_as_uint(m));
+    if (bad) atomicOr(&ctrl->err, IB_ERR_NONFINITE);
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_quantize_kernel(const uint32_t *__restrict__ tid, const float *__restrict__ imp, int64_t n,
+                   int64_t n_tiles, int64_t n_terms, double scale, uint8_t *__restrict__ qval,
+                   uint32_t *__restrict__ tile_kept, unsigned long long *__restrict__ tcount,
+                   Ctrl *__restrict__ ctrl) {
+    __shared__ uint32_t wsum[IB_WAVES];
+    int err = 0;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        uint32_t kept = 0;  // of this wave (the same in all its lanes)
+        for (int r = 0; r < IB_ROUNDS; ++r) {
+            const int64_t i = tile * IB_TILE + (int64_t)r * IB_THREADS + threadIdx.x;
+            bool keep = false;
+            if (i < n) {
+                double p = __dmul_rn((double)imp[i], scale);
+                p = fmin(fmax(p, -2147483648.0), 2147483647.0);
+                const int32_t val = (int32_t)p;  // truncates toward zero, as Python int()
+                const uint32_t t = tid[i];
+                if (t >= n_terms) err |= IB_ERR_TERM;
+                if (val > 255) err |= IB_ERR_RANGE;
+                keep = val > 0 && t < n_terms;
+                qval[i] = (uint8_t)(val > 0 ? min(val, 255) : 0);
+                if (keep) atomicAdd(&tcount[t], 1ull);
+            }
+            kept += (uint32_t)__popcll(__ballot(keep));
+        }
+        if (lane_id() == 0) wsum[wave_id()] = kept;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t s = 0;
+            for (int w = 0; w < IB_WAVES; ++w) s += wsum[w];
+            tile_kept[tile] = s;
+        }
+        __syncthreads();  // wsum is free again
+    }
+    if (err) atomicOr(&ctrl->err, err);
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_compact_kernel(const uint32_t *__restrict__ tid, const uint32_t *__restrict__ doc,
+                  const uint8_t *__restrict__ qval, int64_t n, int64_t n_tiles, int64_t n_terms,
+                  const int64_t *__restrict__ tile_off, int64_t cap, uint4 *__restrict__ out) {
+    __shared__ uint32_t wcnt[IB_WAVES];
+    const int lane = lane_id(), wave = wave_id();
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        int64_t run = tile_off[tile];
+        for (int r = 0; r < IB_ROUNDS; ++r) {
+            const int64_t i0 = tile * IB_TILE + (int64_t)r * IB_THREADS;
+            if (i0 >= n) break;  // (the same for the whole workgroup)
+            const int64_t i = i0 + threadIdx.x;
+            uint32_t q = 0, t = 0;
+            if (i < n) {
+                q = qval[i];
+                t = tid[i];
+            }
+            const bool keep = q > 0 && t < n_terms;
+            const uint64_t m = __ballot(keep);
+            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(m);
+            __syncthreads();
+            uint32_t before = 0, all = 0;
+            for (int w = 0; w < IB_WAVES; ++w) {
+                if (w < wave) before += wcnt[w];
+                all += wcnt[w];
+            }
+            if (keep) {
+                const int64_t pos = run + before + __popcll(m & ((1ull << lane) - 1));
+                if (pos >= 0 && pos < cap) out[pos] = make_uint4(doc[i], t, 255u - q, 0u);
+            }
+            run += all;
+            __syncthreads();  // wcnt is free again
+        }
+    }
+}
+
+// Inclusive sum over the workgroup's threads in thread order; *total = the workgroup's sum.
+__device__ __forceinline__ int64_t block_incl_scan64(int64_t v, int64_t *wtot, int64_t *total) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int64_t y = __shfl_up((long long)v, d, 64);
+        if (lane_id() >= d) v += y;
+    }
+    __syncthreads();  // wtot is free again
+    if (lane_id() == 63) wtot[wave_id()] = v;
+    __syncthreads();
+    int64_t before = 0, all = 0;
+    for (int w = 0; w < IB_WAVES; ++w) {
+        if (w < wave_id()) before += wtot[w];
+        all += wtot[w];
+    }
+    *total = all;
+    return v + before;
+}
+
+// csum[c] = the sum of cnt[c * IB_SCAN_CHUNK, (c + 1) * IB_SCAN_CHUNK)
+__global__ void __launch_bounds__(IB_THREADS)
+ib_scan_sum_kernel(const uint32_t *__restrict__ cnt, int64_t len, int64_t *__restrict__ csum) {
+    __shared__ int64_t wtot[IB_WAVES];
+    const int64_t i0 = (int64_t)blockIdx.x * IB_SCAN_CHUNK + (int64_t)threadIdx.x * IB_SCAN_ITEMS;
+    int64_t v = 0;
+    for (int j = 0; j < IB_SCAN_ITEMS; ++j)
+        if (i0 + j < len) v += cnt[i0 + j];
+    int64_t total;
+    block_incl_scan64(v, wtot, &total);
+    if (threadIdx.x == 0) csum[blockIdx.x] = total;
+}
+
+// One workgroup: csum[0, n_chunks) -> its exclusive scan in place, the total in csum[n_chunks].
+__global__ void __launch_bounds__(IB_THREADS)
+ib_scan_chunks_kernel(int64_t *__restrict__ csum, int64_t n_chunks) {
+    __shared__ int64_t wtot[IB_WAVES];
+    int64_t carry = 0;
+    for (int64_t c0 = 0; c0 < n_chunks; c0 += IB_THREADS) {
+        const int64_t c = c0 + threadIdx.x;
+        const int64_t v = c < n_chunks ? csum[c] : 0;
+        int64_t total;
+        const int64_t inc = block_incl_scan64(v, wtot, &total);
+        if (c < n_chunks) csum[c] = carry + inc - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) csum[n_chunks] = carry;
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_scan_apply_kernel(const uint32_t *__restrict__ cnt, int64_t len,
+                     const int64_t *__restrict__ csum, int64_t *__restrict__ off) {
+    __shared__ int64_t wtot[IB_WAVES];
+    const int64_t i0 = (int64_t)blockIdx.x * IB_SCAN_CHUNK + (int64_t)threadIdx.x * IB_SCAN_ITEMS;
+    uint32_t c[IB_SCAN_ITEMS];
+    int64_t v = 0;
+#pragma unroll
+    for (int j = 0; j < IB_SCAN_ITEMS; ++j) {
+        c[j] = i0 + j < len ? cnt[i0 + j] : 0u;
+        v += c[j];
+    }
+    int64_t total;
+    int64_t at = csum[blockIdx.x] + block_incl_scan64(v, wtot, &total) - v;
+#pragma unroll
+    for (int j = 0; j < IB_SCAN_ITEMS; ++j) {
+        if (i0 + j < len) off[i0 + j] = at;
+        at += c[j];
+    }
+}
+
+// The digit of a record: of 255 - val (by_row false), or of its row from bit `shift` on.
+__device__ __forceinline__ uint32_t ib_digit(const uint4 &r, bool by_row, int shift) {
+    return by_row ? (r.y >> shift) & 255u : r.z & 255u;
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_hist_kernel(const uint4 *__restrict__ src, int64_t n, int64_t n_tiles, bool by_row, int shift,
+               uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[256];
+    static_assert(IB_THREADS == 256, "one thread a digit");
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        h[threadIdx.x] = 0;
+        __syncthreads();
+        for (int r = 0; r < IB_ROUNDS; ++r) {
+            const int64_t i = tile * IB_TILE + (int64_t)r * IB_THREADS + threadIdx.x;
+            if (i < n) atomicAdd(&h[ib_digit(src[i], by_row, shift)], 1u);  // (a count)
+        }
+        __syncthreads();
+        hist[(int64_t)threadIdx.x * n_tiles + tile] = h[threadIdx.x];
+        __syncthreads();  // h is free again
+    }
+}
+
+__global__ void __launch_bounds__(IB_THREADS)
+ib_scatter_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, int64_t n,
+                  int64_t n_tiles, bool by_row, int shift, const int64_t *__restrict__ off,
+                  const int32_t *__restrict__ term_row, int64_t n_terms) {
+    __shared__ int64_t run[256];                // where the next record of a digit goes
+    __shared__ uint32_t wcnt[IB_WAVES][256];    // this round's records of a digit, per wave
+    const int lane = lane_id(), wave = wave_id();
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        run[threadIdx.x] = off[(int64_t)threadIdx.x * n_tiles + tile];
+        for (int w = 0; w < IB_WAVES; ++w) wcnt[w][threadIdx.x] = 0;
+        __syncthreads();
+        for (int r = 0; r < IB_ROUNDS; ++r) {
+            const int64_t i0 = tile * IB_TILE + (int64_t)r * IB_THREADS;
+            if (i0 >= n) break;  // (the same for the whole workgroup)
+            const int64_t i = i0 + threadIdx.x;
+            const bool valid = i < n;
+            uint4 rec = make_uint4(0, 0, 0, 0);
+            if (valid) rec = src[i];
+            const uint32_t d = ib_digit(rec, by_row, shift);
+            uint64_t same = __ballot(valid);  // the valid lanes of this wave with digit d
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint64_t m = __ballot(valid && ((d >> b) & 1u));
+                same &= ((d >> b) & 1u) ? m : ~m;
+            }
+            const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1));
+            if (valid && rank == 0) wcnt[wave][d] = (uint32_t)__popcll(same);
+            __syncthreads();
+            if (valid) {
+                uint32_t before = 0;
+                for (int w = 0; w < wave; ++w) before += wcnt[w][d];
+                const int64_t pos = run[d] + before + rank;
+                if (term_row) rec.y = rec.y < n_terms ? (uint32_t)term_row[rec.y] : 0u;
+                if (pos >= 0 && pos < n) dst[pos] = rec;  // (always: the counts add up to n)
+            }
+            __syncthreads();
+            uint32_t all = 0;
+            for (int w = 0; w < IB_WAVES; ++w) {
+                all += wcnt[w][threadIdx.x];
+                wcnt[w][threadIdx.x] = 0;
+            }
+            run[threadIdx.x] += all;
+            __syncthreads();
+        }
+        __syncthreads();  // run and wcnt are free again
+    }
+}
+
+// Four records a thread: the docs as one 16-byte store and the values as one 4-byte store
+// where the outputs are aligned for it (vec), else one by one.
+__global__ void __launch_bounds__(IB_THREADS)
+ib_extract_kernel(const uint4 *__restrict__ src, int64_t n, uint32_t *__restrict__ pdoc,
+                  uint8_t *__restrict__ pval, bool vec) {
+    for (int64_t q = (int64_t)blockIdx.x * IB_THREADS + threadIdx.x; q * 4 < n;
+         q += (int64_t)gridDim.x * IB_THREADS) {
+        const int64_t i = q * 4;
+        if (vec && i + 3 < n) {
+            const uint4 a = src[i], b = src[i + 1], c = src[i + 2], d = src[i + 3];
+            *reinterpret_cast<uint4 *>(pdoc + i) = make_uint4(a.x, b.x, c.x, d.x);
+            *reinterpret_cast<uchar4 *>(pval + i) =
+                make_uchar4((uint8_t)(255u - a.z), (uint8_t)(255u - b.z), (uint8_t)(255u - c.z),
+                            (uint8_t)(255u - d.z));
+        } else {
+            for (int64_t j = i; j < n && j < i + 4; ++j) {
+                const uint4 a = src[j];
+                pdoc[j] = a.x;
+                pval[j] = (uint8_t)(255u - a.z);
+            }
+        }
+    }
+}
+
+inline int grid_for(int64_t items, int per_block) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block,
+                                                       IB_MAX_GRID));
+}
+
+inline size_t at_least_one(int64_t n) { return (size_t)std::max<int64_t>(n, 1); }
+
+}  // namespace
+}  // namespace di
+
+struct di_index_builder {
+    int device = 0;
+    int64_t n_docs = 0, n_pairs = 0;  // documents and pairs appended
+    di::DevBuf tid, doc, imp;         // the pairs, in document order
+    std::vector<int64_t> empty_docs;  // doc ids of the documents without a pair
+    // the last quantize: the kept records in document order, the kept pairs per term id
+    int64_t n_kept = -1, n_terms = 0;
+    di::DevBuf kept;
+    std::vector<int64_t> tcount;
+    // scratch
+    di::DevBuf in_ids, in_imp, in_cu, ctrl, qval, cnt, off, csum, dcount, sort_a, sort_b, d_row,
+        o_doc, o_val, o_off;
+    di::Timer timer;
+};
+
+using namespace di;
+
+namespace {
+
+void ib_reserve(di_index_builder *b, int64_t n_pairs, hipStream_t s) {
+    const size_t need = at_least_one(n_pairs) * 4, used = (size_t)b->n_pairs * 4;
+    grow_keep(b->tid, need, used, s);
+    grow_keep(b->doc, need, used, s);
+    grow_keep(b->imp, need, used, s);
+}
+
+// off[0, len) = the exclusive scan of cnt[0, len) -> the total (waits for s)
+int64_t ib_scan(di_index_builder *b, const uint32_t *cnt, int64_t len, int64_t *off, bool timing,
+                hipStream_t s) {
+    const int64_t n_chunks = (len + IB_SCAN_CHUNK - 1) / IB_SCAN_CHUNK;
+    DI_REQUIRE(n_chunks <= (int64_t)INT32_MAX, DI_ERANGE, "too many postings for one scan");
+    b->csum.reserve((size_t)(n_chunks + 1) * 8);
+    {
+        TimedLaunch tl(b->timer, timing, "ib_scan", s);
+        hipLaunchKernelGGL(ib_scan_sum_kernel, dim3((unsigned)n_chunks), dim3(IB_THREADS), 0, s, cnt,
+                           len, b->csum.as<int64_t>());
+        check_launch("ib_scan_sum");
+        hipLaunchKernelGGL(ib_scan_chunks_kernel, dim3(1), dim3(IB_THREADS), 0, s,
+                           b->csum.as<int64_t>(), n_chunks);
+        check_launch("ib_scan_chunks");
+        hipLaunchKernelGGL(ib_scan_apply_kernel, dim3((unsigned)n_chunks), dim3(IB_THREADS), 0, s,
+                           cnt, len, b->csum.as<int64_t>(), off);
+        check_launch("ib_scan_apply");
+    }
+    int64_t total = 0;
+    read_back(total, b->csum.as<int64_t>() + n_chunks, s, &b->timer);
+    return total;
+}
+
+}  // namespace
+
+extern "C" {
+
+int di_index_builder_create(int device, di_index_builder **out) {
+    return guard([&] {
+        DI_REQUIRE(out, DI_EINVAL, "null output");
+        *out = nullptr;
+        check_device(device);
+        DeviceScope ds(device);
+        std::unique_ptr<di_index_builder> b(new di_index_builder);
+        b->device = device;
+        b->ctrl.reserve(sizeof(Ctrl));
+        ib_reserve(b.get(), 1, nullptr);
+        *out = b.release();
+    });
+}
+
+int di_index_builder_reserve(di_index_builder *b, int64_t n_docs, int64_t n_pairs) {
+    return guard([&] {
+        DI_REQUIRE(b && n_docs >= 0 && n_pairs >= 0, DI_EINVAL, "bad argument");
+        DI_REQUIRE(n_docs <= (int64_t)UINT32_MAX, DI_ERANGE, "doc ids are 32-bit");
+        DeviceScope ds(b->device);
+        ib_reserve(b, std::max(n_pairs, b->n_pairs), nullptr);
+    });
+}
+
+int di_index_builder_append(di_index_builder *b, const uint32_t *term_ids, const float *impacts,
+                            const int32_t *cu_terms, int32_t n_docs, int64_t *first_doc,
+                            void *hip_stream, uint32_t flags) {
+    return guard([&] {
+        DI_REQUIRE(b && cu_terms && first_doc && n_docs >= 0, DI_EINVAL, "bad argument");
+        DI_REQUIRE(b->n_docs + n_docs <= (int64_t)UINT32_MAX, DI_ERANGE,
+                   "%lld docs: doc ids are 32-bit", (long long)(b->n_docs + n_docs));
+        DeviceScope ds(b->device);
+        const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
+        hipStream_t s = (hipStream_t)hip_stream;
+        *first_doc = b->n_docs;
+        if (n_docs == 0) return;
+        // the offsets are checked on the host before anything changes (with device
+        // pointers a copy of them is read back: 4 bytes a document)
+        std::vector<int32_t> h_cu;
+        const int32_t *cu = host_cu(cu_terms, n_docs, dev, h_cu, s);
+        const int64_t total = check_cu(cu, n_docs, "cu_terms");
+        DI_REQUIRE(total == 0 || (term_ids && impacts), DI_EINVAL, "null input");
+        std::vector<int64_t> empty;
+        for (int32_t d = 0; d < n_docs; ++d)
+            if (cu[d + 1] == cu[d]) empty.push_back(b->n_docs + d);
+        if (total > 0) {
+            ib_reserve(b, b->n_pairs + total, s);
+            const uint32_t *d_ids = stage_in(term_ids, (size_t)total, dev, b->in_ids, s);
+            const float *d_imp = stage_in(impacts, (size_t)total, dev, b->in_imp, s);
+            const int32_t *d_cu = stage_in(cu_terms, (size_t)n_docs + 1, dev, b->in_cu, s);
+            {
+                TimedLaunch tl(b->timer, timing, "ib_append", s);
+                hipLaunchKernelGGL(ib_append_kernel, dim3(grid_for(total, IB_THREADS)),
+                                   dim3(IB_THREADS), 0, s, d_ids, d_imp, d_cu, n_docs, total,
+                                   (uint32_t)b->n_docs, b->n_pairs, b->n_pairs + total,
+                                   b->tid.as<uint32_t>(), b->doc.as<uint32_t>(),
+                                   b->imp.as<float>());
+                check_launch("ib_append");
+            }
+            DI_HIP(hipStreamSynchronize(s));
+            b->timer.resolve();
+        }
+        b->empty_docs.insert(b->empty_docs.end(), empty.begin(), empty.end());
+        b->n_pairs += total;
+        b->n_docs += n_docs;
+        b->n_kept = -1;  // (the kept records are those of the pairs before this append)
+    });
+}
+
+int di_index_builder_info(const di_index_builder *b, int64_t *n_docs, int64_t *n_pairs) {
+    return guard([&] {
+        DI_REQUIRE(b, DI_EINVAL, "null handle");
+        if (n_docs) *n_docs = b->n_docs;
+        if (n_pairs) *n_pairs = b->n_pairs;
+    });
+}
+
+int di_index_builder_quantize(di_index_builder *b, int64_t n_terms, double max_val,
+                              void *hip_stream, uint32_t flags, double *max_used,
+                              int64_t *term_count, int64_t *n_kept) {
+    return guard([&] {
+        DI_REQUIRE(b && n_terms >= 0 && n_kept && (term_count || n_terms == 0), DI_EINVAL,
+                   "bad argument");
+        DI_REQUIRE(n_terms <= (int64_t)UINT32_MAX, DI_ERANGE, "term ids are 32-bit");
+        DI_REQUIRE(b->empty_docs.empty(), DI_EFORMAT,
+                   "document %lld has no terms: its impact line is empty (quantize_file raises "
+                   "ValueError, quantize.py:21)",
+                   (long long)(b->empty_docs.empty() ? 0 : b->empty_docs[0]));
+        DeviceScope ds(b->device);
+        const bool timing = flags & DI_F_TIMING;
+        hipStream_t s = (hipStream_t)hip_stream;
+        const int64_t n = b->n_pairs;
+        const int64_t n_tiles = (n + IB_TILE - 1) / IB_TILE;
+        Ctrl *ctrl = b->ctrl.as<Ctrl>();
+        Ctrl h{};
+        DI_HIP(hipMemsetAsync(ctrl, 0, sizeof(Ctrl), s));
+        if (n > 0) {
+            TimedLaunch tl(b->timer, timing, "ib_quantize", s);
+            hipLaunchKernelGGL(ib_max_kernel, dim3(grid_for(n, IB_THREADS * 8)), dim3(IB_THREADS),
+                               0, s, b->imp.as<float>(), n, ctrl);
+            check_launch("ib_max");
+        }
+        read_back(h, ctrl, s, &b->timer);
+        DI_REQUIRE(!(h.err & IB_ERR_NONFINITE), DI_EFORMAT,
+                   "an impact is not finite (int() of it raises in quantize.py:45)");
+        float mf;
+        std::memcpy(&mf, &h.max_bits, 4);
+        const double m = max_val > 0.0 ? max_val : (double)mf;
+        if (max_used) *max_used = m;
+        DI_REQUIRE(m > 0.0, DI_EINVAL,
+                   "max impact is 0: the reference divides by zero (quantize.py:37)");
+        const double scale = 255.0 / m;
+        b->qval.reserve(at_least_one(n));
+        b->cnt.reserve(at_least_one(n_tiles) * 4);
+        b->off.reserve(at_least_one(n_tiles) * 8);
+        b->dcount.reserve(at_least_one(n_terms) * 8);
+        DI_HIP(hipMemsetAsync(b->dcount.p, 0, at_least_one(n_terms) * 8, s));
+        int64_t total = 0;
+        if (n > 0) {
+            {
+                TimedLaunch tl(b->timer, timing, "ib_quantize", s);
+                hipLaunchKernelGGL(ib_quantize_kernel, dim3(grid_for(n_tiles, 1)),
+                                   dim3(IB_THREADS), 0, s, b->tid.as<uint32_t>(),
+                                   b->imp.as<float>(), n, n_tiles, n_terms, scale,
+                                   b->qval.as<uint8_t>(), b->cnt.as<uint32_t>(),
+                                   b->dcount.as<unsigned long long>(), ctrl);
+                check_launch("ib_quantize");
+            }
+            read_back(h, ctrl, s, &b->timer);
+            DI_REQUIRE(!(h.err & IB_ERR_TERM), DI_EINVAL, "a term id is not below n_terms = %lld",
+                       (long long)n_terms);
+            DI_REQUIRE(!(h.err & IB_ERR_RANGE), DI_ERANGE,
+                       "a value is above 255 with max_val = %.17g (struct.pack('B') fails in "
+                       "create.py:45)", m);
+            total = ib_scan(b, b->cnt.as<uint32_t>(), n_tiles, b->off.as<int64_t>(), timing, s);
+            DI_REQUIRE(total >= 0 && total <= n, DI_EHIP, "ib_quantize kept %lld of %lld pairs",
+                       (long long)total, (long long)n);
+        }
+        // from here on the result of an earlier quantize is replaced
+        b->n_kept = -1;
+        b->kept.reserve(at_least_one(total) * sizeof(uint4));
+        if (total > 0) {
+            TimedLaunch tl(b->timer, timing, "ib_compact", s);
+            hipLaunchKernelGGL(ib_compact_kernel, dim3(grid_for(n_tiles, 1)), dim3(IB_THREADS), 0,
+                               s, b->tid.as<uint32_t>(), b->doc.as<uint32_t>(),
+                               b->qval.as<uint8_t>(), n, n_tiles, n_terms, b->off.as<int64_t>(),
+                               total, b->kept.as<uint4>());
+            check_launch("ib_compact");
+        }
+        b->tcount.assign((size_t)n_terms, 0);
+        if (n_terms > 0)
+            DI_HIP(hipMemcpyAsync(b->tcount.data(), b->dcount.p, (size_t)n_terms * 8,
+                                  hipMemcpyDeviceToHost, s));
+        DI_HIP(hipStreamSynchronize(s));
+        b->timer.resolve();
+        if (n_terms > 0) std::memcpy(term_count, b->tcount.data(), (size_t)n_terms * 8);
+        b->n_terms = n_terms;
+        b->n_kept = total;
+        *n_kept = total;
+    });
+}
+
+int di_index_builder_postings(di_index_builder *b, const int32_t *term_row, int64_t n_rows,
+                              void *hip_stream, uint32_t flags, int64_t *term_off, uint32_t *pdoc,
+                              uint8_t *pval) {
+    return guard([&] {
+        DI_REQUIRE(b && n_rows >= 0 && term_off, DI_EINVAL, "bad argument");
+        DI_REQUIRE(b->n_kept >= 0, DI_EINVAL, "di_index_builder_quantize comes first");
+        DI_REQUIRE(n_rows <= (int64_t)INT32_MAX, DI_ERANGE, "rows are 31-bit");
+        const int64_t n = b->n_kept, n_terms = b->n_terms;
+        DI_REQUIRE(n == 0 || (pdoc && pval), DI_EINVAL, "null output");
+        DI_REQUIRE(n_terms == 0 || term_row, DI_EINVAL, "null term_row");
+        // rows: every term with a kept posting has one, and no row is given twice
+        std::vector<int64_t> h_off((size_t)n_rows + 1, 0);
+        {
+            std::vector<uint8_t> seen((size_t)n_rows, 0);
+            for (int64_t t = 0; t < n_terms; ++t) {
+                const int64_t r = term_row[t];
+                DI_REQUIRE(r >= 0 || b->tcount[(size_t)t] == 0, DI_EINVAL,
+                           "term id %lld keeps %lld postings and has no row", (long long)t,
+                           (long long)b->tcount[(size_t)t]);
+                if (r < 0) continue;
+                DI_REQUIRE(r < n_rows, DI_EINVAL, "term id %lld: row %lld is not below n_rows = %lld",
+                           (long long)t, (long long)r, (long long)n_rows);
+                DI_REQUIRE(!seen[(size_t)r], DI_EINVAL, "row %lld is given to two terms",
+                           (long long)r);
+                seen[(size_t)r] = 1;
+                h_off[(size_t)r + 1] = b->tcount[(size_t)t];
+            }
+            for (int64_t r = 0; r < n_rows; ++r) h_off[(size_t)r + 1] += h_off[(size_t)r];
+        }
+        DeviceScope ds(b->device);
+        const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
+        hipStream_t s = (hipStream_t)hip_stream;
+        if (dev)
+            DI_HIP(hipMemcpyAsync(term_off, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, s));
+        if (n > 0) {
+            int row_passes = 0;
+            for (int64_t top = n_rows - 1; top > 0; top >>= 8) ++row_passes;
+            const int64_t n_tiles = (n + IB_TILE - 1) / IB_TILE, cells = 256 * n_tiles;
+            const int32_t *d_row = stage_in(term_row, (size_t)n_terms, false, b->d_row, s);
+            b->sort_a.reserve((size_t)n * sizeof(uint4));
+            if (row_passes > 0) b->sort_b.reserve((size_t)n * sizeof(uint4));
+            b->cnt.reserve((size_t)cells * 4);
+            b->off.reserve((size_t)cells * 8);
+            const uint4 *src = b->kept.as<uint4>();
+            for (int p = 0; p <= row_passes; ++p) {
+                uint4 *dst = (p % 2 == 0 ? b->sort_a : b->sort_b).as<uint4>();
+                const bool by_row = p > 0;
+                const int shift = by_row ? 8 * (p - 1) : 0;
+                {
+                    TimedLaunch tl(b->timer, timing, "ib_hist", s);
+                    hipLaunchKernelGGL(ib_hist_kernel, dim3(grid_for(n_tiles, 1)),
+                                       dim3(IB_THREADS), 0, s, src, n, n_tiles, by_row, shift,
+                                       b->cnt.as<uint32_t>());
+                    check_launch("ib_hist");
+                }
+                const int64_t total = ib_scan(b, b->cnt.as<uint32_t>(), cells,
+                                              b->off.as<int64_t>(), timing, s);
+                DI_REQUIRE(total == n, DI_EHIP, "ib_hist counted %lld of %lld postings",
+                           (long long)total, (long long)n);
+                {
+                    TimedLaunch tl(b->timer, timing, "ib_scatter", s);
+                    hipLaunchKernelGGL(ib_scatter_kernel, dim3(grid_for(n_tiles, 1)),
+                                       dim3(IB_THREADS), 0, s, src, dst, n, n_tiles, by_row, shift,
+                                       b->off.as<int64_t>(), p == 0 ? d_row : nullptr, n_terms);
+                    check_launch("ib_scatter");
+                }
+                src = dst;
+            }
+            StagedOut<uint32_t> o_doc(pdoc, (size_t)n, dev, b->o_doc);
+            StagedOut<uint8_t> o_val(pval, (size_t)n, dev, b->o_val);
+            const bool vec = (uintptr_t)o_doc.d % 16 == 0 && (uintptr_t)o_val.d % 4 == 0;
+            {
+                TimedLaunch tl(b->timer, timing, "ib_extract", s);
+                hipLaunchKernelGGL(ib_extract_kernel, dim3(grid_for((n + 3) / 4, IB_THREADS)),
+                                   dim3(IB_THREADS), 0, s, src, n, o_doc.d, o_val.d, vec);
+                check_launch("ib_extract");
+            }
+            o_doc.copy_back(s);
+            o_val.copy_back(s);
+        }
+        DI_HIP(hipStreamSynchronize(s));
+        b->timer.resolve();
+        if (!dev) std::memcpy(term_off, h_off.data(), h_off.size() * 8);
+    });
+}
+
+int di_index_builder_timing(di_index_builder *b, const char *name, di_timing *out, int reset) {
+    return guard([&] {
+        DI_REQUIRE(b && name && out, DI_EINVAL, "bad argument");
+        b->timer.get(name, out, reset != 0);
+    });
+}
+
+int di_index_builder_destroy(di_index_builder *b) {
+    return guard([&] {
+        if (!b) return;
+        DeviceScope ds(b->device);
+        delete b;
+    });
+}
+
+}  // extern "C"

@@ -26,6 +26,7 @@
 
 #include "di_common.h"
 #include "pytext.h"
+#include "term_table.h"
 
 namespace {
 
@@ -308,22 +309,65 @@ extern "C" int di_build_reference_index(const char *collection_path, const char 
                 }
             }
         });
-        std::vector<uint64_t> idx(V * 2);
-        for (size_t t = 0; t < V; ++t) {
-            idx[2 * t] = (uint64_t)toff[t] * 5;
-            idx[2 * t + 1] = (uint64_t)toff[t + 1] * 5;
-        }
-        std::string vtxt;
-        size_t vbytes = 0;
-        for (auto t : vocab) vbytes += t.size() + 1;
-        vtxt.reserve(vbytes);
-        for (auto t : vocab) {
-            vtxt.append(t.data(), t.size());
-            vtxt += '\n';
-        }
-        std::string od(out_dir);
-        write_all(od + "/vocab.txt", vtxt.data(), vtxt.size());
-        write_all(od + "/inverted_index.dat", dat.data(), dat.size());
-        write_all(od + "/inverted_index.idx", idx.data(), idx.size() * 8);
+        write_reference_files(out_dir, vocab, toff.data(), dat.data());
     });
+}
+
+// The same three files from the CSR di_index_builder_postings returns (rows already in
+// vocab.txt order, postings in file order) and the table that numbered the terms.
+extern "C" int di_write_reference_index(const char *out_dir, const di_term_table *table,
+                                        const int32_t *term_row, int64_t n_rows,
+                                        const int64_t *term_off, const uint32_t *pdoc,
+                                        const uint8_t *pval) {
+    return guard([&] {
+        DI_REQUIRE(out_dir && table && term_off && n_rows >= 0, DI_EINVAL, "null argument");
+        DI_REQUIRE(table->terms.empty() || term_row, DI_EINVAL, "null term_row");
+        std::vector<std::string_view> vocab((size_t)n_rows);
+        std::vector<uint8_t> seen((size_t)n_rows, 0);
+        for (size_t t = 0; t < table->terms.size(); ++t) {
+            const int64_t r = term_row[t];
+            if (r < 0) continue;
+            DI_REQUIRE(r < n_rows && !seen[(size_t)r], DI_EINVAL,
+                       "term id %lld: row %lld is out of range or given twice", (long long)t,
+                       (long long)r);
+            seen[(size_t)r] = 1;
+            vocab[(size_t)r] = table->terms[t];
+        }
+        for (int64_t r = 0; r < n_rows; ++r) {
+            DI_REQUIRE(seen[(size_t)r], DI_EINVAL, "row %lld has no term", (long long)r);
+            DI_REQUIRE(term_off[r + 1] >= term_off[r] && term_off[0] == 0, DI_EINVAL,
+                       "term_off not monotone at %lld", (long long)r);
+        }
+        const int64_t n = n_rows ? term_off[n_rows] : 0;
+        DI_REQUIRE(n == 0 || (pdoc && pval), DI_EINVAL, "null postings");
+        std::vector<unsigned char> dat((size_t)n * 5);
+        parallel_for(n, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t i = lo; i < hi; ++i) {
+                std::memcpy(&dat[(size_t)i * 5], &pdoc[i], 4);
+                dat[(size_t)i * 5 + 4] = pval[i];
+            }
+        });
+        write_reference_files(out_dir, vocab, term_off, dat.data());
+    });
+}
+
+void di::write_reference_files(const std::string &od, const std::vector<std::string_view> &vocab,
+                               const int64_t *toff, const unsigned char *dat) {
+    const size_t V = vocab.size();
+    std::vector<uint64_t> idx(V * 2);
+    for (size_t t = 0; t < V; ++t) {
+        idx[2 * t] = (uint64_t)toff[t] * 5;
+        idx[2 * t + 1] = (uint64_t)toff[t + 1] * 5;
+    }
+    std::string vtxt;
+    size_t vbytes = 0;
+    for (auto t : vocab) vbytes += t.size() + 1;
+    vtxt.reserve(vbytes);
+    for (auto t : vocab) {
+        vtxt.append(t.data(), t.size());
+        vtxt += '\n';
+    }
+    write_all(od + "/vocab.txt", vtxt.data(), vtxt.size());
+    write_all(od + "/inverted_index.dat", dat, V ? (size_t)toff[V] * 5 : 0);
+    write_all(od + "/inverted_index.idx", idx.data(), idx.size() * 8);
 }

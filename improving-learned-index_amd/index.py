@@ -11,6 +11,12 @@ Output bytes are those of the reference (one line per input line, in order).
 --pairwise loads the checkpoint as DeepPairwiseImpact (models/pairwise_impact.py) and adds
 each passage's 't1|t2' pair entries, the line sorted by score (the call the reference's
 indexer.py:49-54 holds in a comment).
+--inverted_index_path DIR builds the quantized inverted index (vocab.txt, inverted_index.idx,
+inverted_index.dat) in DIR in the same process, from the encoder's device output: the bytes
+of `quantize` and `inverted_index` run over the impact TSV, without that file (--max_val:
+quantize's -m; --output_file_path is then optional and still writes the TSV).  One GPU:
+not with --pairwise, --doc_range or more than one rank.  DI_INDEX_TEXT_ROUTE=1 runs the
+three text steps into DIR instead (A/B).
 Multi-GPU: --doc_range start:end encodes one doc-id shard; concatenating the
 shard outputs in order gives the single-GPU file.  Under torchrun
 (--nproc-per-node N) every rank encodes doc-id shard r on its GPU and rank 0 joins
@@ -28,7 +34,8 @@ from pathlib import Path
 
 from . import parallel
 from .datasets import COLLECTION_TYPES, CollectionParser
-from .indexer import Indexer, TokenizerPool, pool_supported, resolve_tokenizer
+from .indexer import (IndexBuild, Indexer, TokenizerPool, pool_supported,
+                      resolve_tokenizer)
 from .models import DeepImpact, DeepPairwiseImpact
 
 BATCH_SIZE = 32  # src/utils/defaults.py:15
@@ -39,7 +46,11 @@ logger = logging.getLogger("index")
 def run(collection_path, collection_type, output_file_path, model_checkpoint_path,
         num_processes=8, process_batch_size=50 * BATCH_SIZE, model_batch_size=BATCH_SIZE,
         tokenizer_path=None, max_length=None, precision="bf16x3", device=0, variant="xlmr",
-        doc_range=None, pairwise=False, first_shard=True):
+        doc_range=None, pairwise=False, first_shard=True, inverted_index_path=None,
+        max_val=None):
+    """inverted_index_path: build the quantized index there on the device
+    (Indexer.build_index's route) instead of / beside the impact TSV; output_file_path may
+    then be None."""
     # --pairwise: DeepPairwiseImpact through the same Indexer (its lines add the
     # 't1|t2' entries and are sorted by score, pairwise_impact.py:98-129)
     model_cls = DeepPairwiseImpact if pairwise else DeepImpact
@@ -56,6 +67,17 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
                                max_length=max_length)
         indexer = Indexer(model, model_batch_size=model_batch_size,
                           num_processes=num_processes, pool=pool)
+        if inverted_index_path is not None:
+            # the same loop over the same batches (and the same TSV bytes, when asked for),
+            # the impacts kept on the device
+            build = IndexBuild(indexer, write_tsv=output_file_path is not None)
+            n = _index_file(build, collection_path, collection_type,
+                            output_file_path if output_file_path is not None else os.devnull,
+                            process_batch_size, doc_range, start, first_shard)
+            build.inverted_index(max_val, inverted_index_path)
+            logger.info(f"Built the inverted index of {n} passages in {inverted_index_path} "
+                        f"(max value {build.max_used})")
+            return n
         return _index_file(indexer, collection_path, collection_type, output_file_path,
                            process_batch_size, doc_range, start, first_shard)
     finally:
@@ -120,11 +142,52 @@ def _index_file(indexer, collection_path, collection_type, output_file_path,
     return n
 
 
+ONE_GPU = ("--inverted_index_path builds the index on one GPU: pass --device or --gpus 1 "
+           "(a sharded build is not implemented)")
+
+
+def _check_index_route(p, a):
+    """--inverted_index_path: one process, the whole collection, the single-term model."""
+    if a.pairwise:
+        p.error("--inverted_index_path does not take --pairwise: the pairwise collection goes "
+                "through the text route (index, quantize, inverted_index)")
+    if a.doc_range is not None:
+        p.error("--inverted_index_path does not take --doc_range. " + ONE_GPU)
+    if parallel.dist_env()[0] > 1 or (a.device is None and parallel.ranks_to_spawn(a.gpus) > 1):
+        p.error(ONE_GPU)
+    a.gpus = 1  # (checked: this process alone)
+
+
+def _text_route(a):
+    """DI_INDEX_TEXT_ROUTE=1: the same directory by the three text steps -- index,
+    quantize, inverted_index -- for A/B runs; the bytes are the same."""
+    import tempfile
+
+    from .inverted_index import create_index
+    from .quantize import quantize_file
+
+    device = a.device or 0
+    with tempfile.TemporaryDirectory() as tmp:
+        tsv = a.output_file_path if a.output_file_path is not None else Path(tmp) / "collection.index"
+        run(a.collection_path, a.collection_type, tsv, a.model_checkpoint_path, a.num_processes,
+            a.process_batch_size, a.model_batch_size, a.tokenizer_path, a.max_length, a.precision,
+            device, a.variant)
+        quantize_file(tsv, Path(tmp) / "collection.quantized", a.max_val, device, sharded=False)
+        create_index(Path(tmp) / "collection.quantized", a.inverted_index_path)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser("Create a DeepImpact index by computing impacts of all document terms.")
     p.add_argument("--collection_path", type=Path, required=True)
     p.add_argument("--collection_type", type=str, default="msmarco", choices=COLLECTION_TYPES)
-    p.add_argument("--output_file_path", type=Path, required=True)
+    p.add_argument("--output_file_path", type=Path, default=None,
+                   help="the impact TSV (required unless --inverted_index_path is given)")
+    p.add_argument("--inverted_index_path", type=Path, default=None,
+                   help="build the quantized inverted index (vocab.txt, inverted_index.idx, "
+                        "inverted_index.dat) in this directory from the encoder's device "
+                        "output, without the intermediate files; one GPU")
+    p.add_argument("--max_val", type=float, default=None,
+                   help="with --inverted_index_path: quantize's -m (default: the maximum)")
     p.add_argument("--model_checkpoint_path", type=str, required=True)
     p.add_argument("--num_processes", type=int, default=8)
     p.add_argument("--process_batch_size", type=int, default=50 * BATCH_SIZE)
@@ -145,6 +208,14 @@ def main(argv=None):
     p.add_argument("--doc_range", type=str, default=None, help="start:end line range (shard)")
     argv = list(sys.argv[1:] if argv is None else argv)
     a = p.parse_args(argv)
+    if a.output_file_path is None and a.inverted_index_path is None:
+        p.error("the following arguments are required: --output_file_path")
+    if a.max_val is not None and a.inverted_index_path is None:
+        p.error("--max_val goes with --inverted_index_path")
+    if a.inverted_index_path is not None:
+        _check_index_route(p, a)
+        if os.environ.get("DI_INDEX_TEXT_ROUTE") == "1":
+            return _text_route(a)
     if a.doc_range is None and a.device is None:
         n = parallel.ranks_to_spawn(a.gpus)
         if n > 1:
@@ -164,7 +235,8 @@ def main(argv=None):
         out, device = parallel.part_path(a.output_file_path, rank), parallel.rank_device(local)
     run(a.collection_path, a.collection_type, out, a.model_checkpoint_path,
         a.num_processes, a.process_batch_size, a.model_batch_size, a.tokenizer_path,
-        a.max_length, a.precision, device, a.variant, dr, a.pairwise, first_shard=rank == 0)
+        a.max_length, a.precision, device, a.variant, dr, a.pairwise, first_shard=rank == 0,
+        inverted_index_path=a.inverted_index_path, max_val=a.max_val)
     if world > 1:
         dist.barrier()
         if rank == 0:

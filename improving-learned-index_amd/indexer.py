@@ -266,6 +266,153 @@ class Indexer:
         """indexer.py:31-68: file.write('\\n'.join(lines) + '\\n')."""
         self.finish(self.submit(batch), file)
 
+    def build_index(self, documents_or_batches, max_val=None, index_path=None, file=None):
+        """Index these documents and search them, in one process: the InvertedIndex the text
+        route (index -> quantize -> inverted_index -> InvertedIndex(path)) gives for the
+        same collection, without its files.  The round3 impacts of every device step stay
+        on the GPU and go to an IndexBuilder; the terms are numbered by a TermTable from
+        the tokenizer's blob.  documents_or_batches: a sequence of passages, or an iterable
+        of such batches (document ids count on across them).  max_val: quantize's -m.
+        index_path: also write vocab.txt / inverted_index.idx / inverted_index.dat there.
+        file: also write the impact TSV there, from the same encode."""
+        docs = documents_or_batches
+        batches = [docs] if isinstance(docs, (list, tuple)) and (not docs or isinstance(docs[0], str)) \
+            else docs
+        build = IndexBuild(self, write_tsv=file is not None)
+        pending = None
+        for batch in batches:  # tokenized one batch ahead, as index.py's loop
+            handle = build.submit(batch)
+            if pending is not None:
+                build.finish(pending, file)
+            pending = handle
+        if pending is not None:
+            build.finish(pending, file)
+        ix = build.inverted_index(max_val, index_path)
+        self.build_ms, self.last_build = build.ms, build
+        return ix
+
+
+class IndexBuild:
+    """The device route from documents to the quantized index, one batch at a time: the
+    submit / finish protocol of Indexer (so index.py's loop drives either), the impacts
+    appended to an IndexBuilder instead of formatted -- and formatted as well when the
+    impact TSV is wanted (write_tsv: the bytes of Indexer.index)."""
+
+    def __init__(self, indexer: "Indexer", write_tsv: bool = True):
+        from .models import DeepPairwiseImpact
+
+        model = indexer.model
+        if isinstance(model, DeepPairwiseImpact) or not hasattr(model, "encoder"):
+            raise ValueError("the device index route needs a DeepImpact model on a DeviceEncoder "
+                             "(the pairwise collection goes through the text route)")
+        self.indexer, self.model, self.write_tsv = indexer, model, write_tsv
+        self.device = getattr(model.encoder, "device", 0) or 0
+        self.table = _lib.TermTable()
+        self.builder = _lib.IndexBuilder(self.device)
+        self.ms = {"tokenize": 0.0, "encode": 0.0, "build": 0.0}
+
+    def submit(self, batch: Sequence[str]):
+        return self.indexer.submit(batch)
+
+    def _packed_steps(self, handle):
+        """The batch as pack_processed_blob device steps of up to DEVICE_DOCS documents."""
+        import time
+
+        batch, it = handle
+        if it is None:
+            def chunks():
+                for c in self.indexer._chunks(batch):
+                    yield DeepImpact.pack_processed_blob(
+                        self.model.process_documents(c, self.model.max_length))
+            it = chunks()
+        parts, n = [], 0
+        while True:
+            t0 = time.perf_counter()
+            p = next(it, None)
+            self.ms["tokenize"] += (time.perf_counter() - t0) * 1e3
+            if p is None:
+                break
+            parts.append(p)
+            n += len(p[1]) - 1
+            if n >= DEVICE_DOCS:
+                yield DeepImpact.merge_packed_blobs(parts)
+                parts, n = [], 0
+        if parts:
+            yield DeepImpact.merge_packed_blobs(parts)
+
+    def _step(self, packed) -> str:
+        import time
+
+        import numpy as np
+        import torch
+
+        ids, cu, blob, term_off, tt, ct = packed
+        t0 = time.perf_counter()
+        dev = torch.device("cuda", self.device)
+        n_docs, n_terms = len(cu) - 1, int(ct[-1])
+        tid = self.table.intern(blob, term_off).view(np.int32)
+        pad = lambda a: a if a.size else np.zeros(1, np.int32)  # noqa: E731
+        d_ids = torch.from_numpy(pad(np.ascontiguousarray(ids, np.int32))).to(dev)
+        d_cu = torch.from_numpy(np.ascontiguousarray(cu, np.int32)).to(dev)
+        d_tt = torch.from_numpy(pad(np.ascontiguousarray(tt, np.int32))).to(dev)
+        d_ct = torch.from_numpy(np.ascontiguousarray(ct, np.int32)).to(dev)
+        d_tid = torch.from_numpy(pad(tid)).to(dev)
+        d_imp = torch.empty(max(1, n_terms), dtype=torch.float32, device=dev)
+        t1 = time.perf_counter()
+        # synchronous at return (no DI_F_ASYNC): the builder's stream may read d_imp
+        self.model.encoder.encode_device(d_ids, d_cu, n_docs, int(cu[-1]),
+                                         int(np.diff(cu).max(initial=0)), d_tt, d_ct, n_terms,
+                                         d_imp, flags=_lib.DI_F_DEVICE_PTRS | _lib.DI_F_ROUND3)
+        t2 = time.perf_counter()
+        self.builder.append(d_tid, d_imp, d_ct, timing=True)
+        text = ""
+        if self.write_tsv:
+            text = _lib.format_impact_lines_packed(blob, term_off, d_imp[:n_terms].cpu().numpy(), ct)
+        t3 = time.perf_counter()
+        self.ms["encode"] += (t2 - t1) * 1e3
+        self.ms["build"] += (t1 - t0 + t3 - t2) * 1e3
+        return text
+
+    def finish(self, handle, file, wait: bool = True) -> None:
+        import numpy as np
+
+        batch = handle[0]
+        if not batch:
+            # the reference writes an empty line for an empty batch (indexer.py:68): a
+            # document without terms, which quantize refuses on either route
+            self.builder.append(np.zeros(0, np.uint32), np.zeros(0, np.float32),
+                                np.zeros(2, np.int32))
+            text = "\n"
+        else:
+            text = "".join(self._step(p) for p in self._packed_steps(handle))
+        if self.write_tsv and file is not None:
+            file.write(text)
+            file.flush()
+
+    def index(self, batch: Sequence[str], file) -> None:
+        self.finish(self.submit(batch), file)
+
+    def drain(self) -> None:
+        pass
+
+    def inverted_index(self, max_val=None, index_path=None):
+        """Quantize, number the terms, fetch the postings (sorted on the GPU) and create the
+        device index -> InvertedIndex."""
+        import time
+
+        from .inverted_index import InvertedIndex
+
+        if max_val is not None and max_val == 0:
+            raise ZeroDivisionError("float division by zero")  # quantize.py:37
+        if max_val is not None and max_val < 0:
+            raise ValueError("a negative max_val empties every line: use the text route")
+        t0 = time.perf_counter()
+        self.max_used, _, _ = self.builder.quantize(len(self.table), max_val, timing=True)
+        ix = InvertedIndex.from_builder(self.builder, self.table, device=self.device,
+                                        index_path=index_path, timing=True)
+        self.ms["build"] += (time.perf_counter() - t0) * 1e3
+        return ix
+
 
 def resolve_tokenizer(model_checkpoint_path, tokenizer_path):
     """The tokenizer DeepImpact.load would pick (explicit path, else the checkpoint

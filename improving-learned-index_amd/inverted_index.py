@@ -48,6 +48,32 @@ class InvertedIndex:
         self.packed = False
         self.packed_bytes = self.set_packed(packed) if packed else 0
 
+    @classmethod
+    def from_builder(cls, builder: "_lib.IndexBuilder", table: "_lib.TermTable", device=None,
+                     doc_lo: int = 0, doc_hi: int = 0, index_path=None, timing=False):
+        """The index of a quantized IndexBuilder, without the files in between: the same
+        object as InvertedIndex(path) over the files the text route writes for the same
+        collection.  The builder's postings come back in file order (sorted on the GPU) and
+        go through di_index_create; ``vocab`` is the table's terms that kept a posting, in
+        sorted() order.  index_path: also write vocab.txt / inverted_index.idx /
+        inverted_index.dat there."""
+        if getattr(builder, "term_count", None) is None:
+            raise ValueError("IndexBuilder.quantize comes first")
+        term_row, n_rows = table.rows(builder.term_count)
+        term_off, pdoc, pval = builder.postings(term_row, n_rows, timing=timing)
+        if index_path is not None:
+            _lib.write_reference_index(index_path, table, term_row, n_rows, term_off, pdoc, pval)
+        self = cls.__new__(cls)
+        self.index_path = Path(index_path) if index_path is not None else None
+        self.vocab = table.vocab(term_row)
+        self.device = builder.device if device is None else device
+        self.doc_lo, self.doc_hi = doc_lo, doc_hi
+        self._dev = DeviceIndex.from_postings(term_off, pdoc, pval, doc_lo, doc_hi, self.device)
+        self.set_min_impact(1)
+        self.set_block_max(0.0)
+        self.packed, self.packed_bytes = False, 0
+        return self
+
     def set_min_impact(self, min_impact: int) -> None:
         """Query-time impact pruning (config 5): score only postings of value >= the
         largest power of two <= min_impact (1 = every posting = the reference's exact

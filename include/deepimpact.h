@@ -267,6 +267,91 @@ int di_sparse_export(const di_sparse *sp, int64_t *term_start, uint32_t *blk_off
                      uint16_t *pdoc, float *pimp);
 
 /* ======================================================================
+ * Quantized index from the encoder's device output          (A10, A11)
+ * ====================================================================== */
+/* ---- term table: term strings (UTF-8) numbered in order of first appearance ---- */
+typedef struct di_term_table di_term_table;
+
+int di_term_table_create(di_term_table **out);
+/* ids[i] = the id of term i of the batch, blob[term_off[i] .. term_off[i + 1]) (the
+ * packed form the tokenizer workers return); a new term gets the next id.  A term the
+ * text route would parse differently -- empty, with leading or trailing whitespace
+ * (str.strip's), or holding ', ', ': ' or a line break (quantize.py:21-22,
+ * deep_impact_collection.py:20-27) -- is DI_EFORMAT and the table is as before the
+ * call; a bare ',' ':' or '|' inside a term is fine. */
+int di_term_table_intern(di_term_table *t, const char *blob, const int64_t *term_off, int64_t n,
+                         uint32_t *ids);
+int di_term_table_info(const di_term_table *t, int64_t *n_terms, int64_t *n_bytes);
+/* Every term in id order: blob[n_bytes], term_off[n_terms + 1]. */
+int di_term_table_export(const di_term_table *t, char *blob, int64_t *term_off);
+/* term_row[id] = the row of every term with term_count[id] > 0 when those are sorted
+ * by their UTF-8 bytes -- sorted() on str, the order of vocab.txt (create.py:24-27) --
+ * and -1 for every other term; *n_rows = the terms that have a row. */
+int di_term_table_rows(const di_term_table *t, const int64_t *term_count, int32_t *term_row,
+                       int64_t *n_rows);
+int di_term_table_destroy(di_term_table *t);
+
+/* ---- device builder: documents as (term id, impact) pairs, e.g. di_encode's device
+ * output, to the CSR di_index_create takes ---- */
+typedef struct di_index_builder di_index_builder;
+
+#define DI_INDEX_BUILD_TILE 4096 /* pairs / postings one workgroup counts and places */
+
+int di_index_builder_create(int device, di_index_builder **out);
+/* Room for n_pairs pairs in all (optional: the pair buffers grow by reallocation). */
+int di_index_builder_reserve(di_index_builder *b, int64_t n_docs, int64_t n_pairs);
+/* Appends n_docs documents; document d holds (term_ids[i], impacts[i]) for i in
+ * [cu_terms[d], cu_terms[d + 1]) and gets doc id *first_doc + d (append order = the line
+ * number of the impact TSV).  impacts: the DI_F_ROUND3 values, the ones the TSV holds.
+ * Every pair is kept whatever its value (12 bytes: term id, doc, impact), pair i of the
+ * call at end + i; a document without a pair is remembered by its doc id.  Arguments and
+ * flags as di_sparse_builder_append: with DI_F_DEVICE_PTRS the three arrays are device
+ * pointers and only cu_terms is read back.  Runs on hip_stream and waits for it.
+ * cu_terms not starting at 0 or decreasing: DI_EINVAL; more than 2^32 - 1 documents in
+ * all: DI_ERANGE; after an error the builder is as it was before the call.  An append
+ * discards the result of an earlier quantize.  DI_F_TIMING: "ib_append". */
+int di_index_builder_append(di_index_builder *b, const uint32_t *term_ids, const float *impacts,
+                            const int32_t *cu_terms, int32_t n_docs, int64_t *first_doc,
+                            void *hip_stream, uint32_t flags);
+int di_index_builder_info(const di_index_builder *b, int64_t *n_docs, int64_t *n_pairs);
+/* quantize_file (quantize.py:13-47) on everything appended: max_val <= 0 means the
+ * maximum over all pairs, starting from 0 (:17-24); scale = 255 / max_val in fp64;
+ * val = int(double(impact) * scale), truncating (:37-45, di_quantize's arithmetic); a
+ * pair is kept iff val > 0 (:46).  term_count[t] (host, n_terms entries) = the kept pairs
+ * of term id t; *n_kept = their sum; *max_used = the maximum used.  Errors are the text
+ * route's for the same data: a remembered document without a pair (quantize_file raises
+ * on its empty line) DI_EFORMAT, naming it; a non-finite impact DI_EFORMAT; maximum 0
+ * with no max_val DI_EINVAL, as di_quantize; a value above 255 (struct.pack('B') fails,
+ * create.py:45) DI_ERANGE; a term id >= n_terms DI_EINVAL (device-side conditions: an
+ * error word read once per step).  After an error the builder is as it was before the
+ * call, the result of an earlier quantize included.  May be called again with another
+ * max_val: the float impacts stay.  Runs on hip_stream and waits for it.
+ * DI_F_TIMING: "ib_quantize", "ib_scan", "ib_compact". */
+int di_index_builder_quantize(di_index_builder *b, int64_t n_terms, double max_val,
+                              void *hip_stream, uint32_t flags, double *max_used,
+                              int64_t *term_count, int64_t *n_kept);
+/* The kept postings in the reference file order -- row-major by term_row (host,
+ * n_terms entries, -1 = no row), value descending, doc ascending (create.py:41, a stable
+ * sort of a doc-ordered list) -- as the input of di_index_create: term_off[n_rows + 1],
+ * pdoc[n_kept], pval[n_kept]; host pointers, or device pointers with DI_F_DEVICE_PTRS.
+ * A term with kept postings and no row, a row >= n_rows, or two terms on one row:
+ * DI_EINVAL.  The builder is left unchanged: the same call gives the same bytes.
+ * Runs on hip_stream and waits for it.  DI_F_TIMING: "ib_hist", "ib_scan", "ib_scatter",
+ * "ib_extract". */
+int di_index_builder_postings(di_index_builder *b, const int32_t *term_row, int64_t n_rows,
+                              void *hip_stream, uint32_t flags, int64_t *term_off,
+                              uint32_t *pdoc, uint8_t *pval);
+int di_index_builder_timing(di_index_builder *b, const char *name, di_timing *out, int reset);
+int di_index_builder_destroy(di_index_builder *b);
+
+/* vocab.txt, inverted_index.idx and inverted_index.dat in out_dir from
+ * di_index_builder_postings' host arrays and the table's rows: the bytes
+ * di_build_reference_index writes for the same collection (create.py:45-51). */
+int di_write_reference_index(const char *out_dir, const di_term_table *table,
+                             const int32_t *term_row, int64_t n_rows, const int64_t *term_off,
+                             const uint32_t *pdoc, const uint8_t *pval);
+
+/* ======================================================================
  * Encoder: DeepImpact forward + first-occurrence gather     (A2, A5-A9)
  * ====================================================================== */
 typedef struct di_encoder di_encoder;
