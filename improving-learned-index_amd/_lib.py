@@ -151,16 +151,21 @@ SIGNATURES = {
     "di_term_table_info": (ctypes.c_int, [P, P, P]),
     "di_term_table_export": (ctypes.c_int, [P, P, P]),
     "di_term_table_rows": (ctypes.c_int, [P, P, P, P]),
+    "di_term_table_rows_pairwise": (ctypes.c_int, [P, P, I64, P, P, P, P]),
     "di_term_table_destroy": (ctypes.c_int, [P]),
     "di_index_builder_create": (ctypes.c_int, [ctypes.c_int, P]),
     "di_index_builder_reserve": (ctypes.c_int, [P, I64, I64]),
     "di_index_builder_append": (ctypes.c_int, [P, P, P, P, I32, P, P, U32]),
+    "di_index_builder_append_pairwise": (ctypes.c_int, [P, P, P, P, P, P, I32, I64, P, P, U32]),
+    "di_index_builder_pair_terms": (ctypes.c_int, [P, P, P, P, P]),
     "di_index_builder_info": (ctypes.c_int, [P, P, P]),
     "di_index_builder_quantize": (ctypes.c_int, [P, I64, ctypes.c_double, P, U32, P, P, P]),
     "di_index_builder_postings": (ctypes.c_int, [P, P, I64, P, U32, P, P, P]),
     "di_index_builder_timing": (ctypes.c_int, [P, ctypes.c_char_p, P, ctypes.c_int]),
     "di_index_builder_destroy": (ctypes.c_int, [P]),
     "di_write_reference_index": (ctypes.c_int, [ctypes.c_char_p, P, P, I64, P, P, P]),
+    "di_write_reference_index_pairwise": (ctypes.c_int, [ctypes.c_char_p, P, I64, P, P, P, I64,
+                                                         P, P, P]),
     "di_synth_postings": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P, P, I64,
                                          P, P]),
     "di_synth_postings_skewed": (ctypes.c_int, [I64, I32, U64, I32, I32, ctypes.c_double, P, P,
@@ -917,12 +922,41 @@ class TermTable(_Handle):
                                        ctypes.byref(n)))
         return row[:term_count.size], n.value
 
-    def vocab(self, term_row) -> dict:
-        """{term: row} of the terms that have a row (InvertedIndex.vocab)."""
+    def rows_pairwise(self, term_count, first_id, second_id):
+        """rows() over the single terms and the pair terms of IndexBuilder.pair_terms ->
+        (term_row int32 [n_terms + n_pair_terms], n_rows): pair u, named term[first_id[u]] +
+        '|' + term[second_id[u]], is entry n_terms + u.  Two entries with one name: DIError
+        DI_EFORMAT naming it (the text route merges them: build that collection there)."""
+        term_count = np.ascontiguousarray(term_count, np.int64)
+        first_id = np.ascontiguousarray(first_id, np.uint32)
+        second_id = np.ascontiguousarray(second_id, np.uint32)
+        if term_count.size != len(self) or first_id.size != second_id.size:
+            raise ValueError("term_count: one entry per term of the table; one id pair per pair term")
+        n_pt = first_id.size
+        row = np.full(max(term_count.size + n_pt, 1), -1, np.int32)
+        n = I64(0)
+        one = np.zeros(1, np.uint32)
+        check(lib().di_term_table_rows_pairwise(
+            self._h, ptr(term_count if term_count.size else np.zeros(1, np.int64)), n_pt,
+            ptr(first_id if n_pt else one), ptr(second_id if n_pt else one), ptr(row),
+            ctypes.byref(n)))
+        return row[:term_count.size + n_pt], n.value
+
+    def vocab(self, term_row, first_id=None, second_id=None) -> dict:
+        """{term: row} of the terms that have a row (InvertedIndex.vocab); with the pair
+        terms' ids, term_row holds their rows after the single terms' and the pairs are
+        named 'a|b'."""
         blob, off = self.export()
         ol = off.tolist()
-        return {blob[ol[i]:ol[i + 1]].decode("utf-8"): r
-                for i, r in enumerate(np.asarray(term_row).tolist()) if r >= 0}
+        names = [blob[ol[i]:ol[i + 1]].decode("utf-8") for i in range(len(ol) - 1)]
+        rows = np.asarray(term_row).tolist()
+        v = {names[i]: r for i, r in enumerate(rows[:len(names)]) if r >= 0}
+        if first_id is not None:
+            for a, b, r in zip(np.asarray(first_id).tolist(), np.asarray(second_id).tolist(),
+                               rows[len(names):]):
+                if r >= 0:
+                    v[names[a] + "|" + names[b]] = r
+        return v
 
 
 class IndexBuilder(_TimedHandle):
@@ -959,6 +993,53 @@ class IndexBuilder(_TimedHandle):
         if n_docs > 0:
             self.n_kept, self.term_count = None, None
         return first.value
+
+    def append_pairwise(self, term_ids, single, pair, cu_terms, cu_pairs, stream=0, timing=False):
+        """Appends len(cu_terms) - 1 documents of the pairwise model from encode_pairwise's
+        unrounded outputs (round3 is applied here): the singles as append() takes them, the
+        terms in token order; pair / cu_pairs (int64) the scores of every document's
+        T(T-1)/2 combinations, kept iff they do not round to zero, each the posting of the
+        term 'a|b'.  Host numpy arrays, or torch device tensors (all five).  Returns the doc
+        id of the first appended document."""
+        n_docs = len(cu_terms) - 1
+        if len(cu_pairs) != n_docs + 1:
+            raise ValueError("cu_terms and cu_pairs: one entry per document + 1")
+        if _is_device(cu_terms):
+            if not all(_is_device(x) for x in (term_ids, single, pair, cu_pairs)):
+                raise ValueError("append_pairwise: all five arrays on the device, or none")
+            if cu_pairs.element_size() != 8 or cu_terms.element_size() != 4:
+                raise ValueError("cu_terms is int32 and cu_pairs int64")
+            n_pairs = int(cu_pairs[-1]) if n_docs > 0 else 0
+            flags = (DI_F_TIMING if timing else 0) | DI_F_DEVICE_PTRS
+        else:
+            term_ids, single, cu_terms, n_docs, flags = _append_arrays(term_ids, single,
+                                                                      cu_terms, timing)
+            pair = np.ascontiguousarray(pair, np.float32)
+            cu_pairs = np.ascontiguousarray(cu_pairs, np.int64)
+            n_pairs = int(cu_pairs[-1]) if n_docs > 0 else 0
+            if pair.size < n_pairs:
+                raise ValueError("pair: one entry per pair of cu_pairs")
+            if pair.size == 0:
+                pair = np.zeros(1, np.float32)
+        first = I64(0)
+        check(lib().di_index_builder_append_pairwise(
+            self._h, ptr(term_ids), ptr(single), ptr(pair), ptr(cu_terms), ptr(cu_pairs), n_docs,
+            n_pairs, ctypes.byref(first), ctypes.c_void_p(stream or 0), flags))
+        if n_docs > 0:
+            self.n_kept, self.term_count = None, None
+        return first.value
+
+    def pair_terms(self):
+        """The distinct pair keys that kept a posting in the last quantize, in ascending
+        (first id, second id) order -> (first_id uint32, second_id uint32, count int64)."""
+        n = I64(0)
+        check(lib().di_index_builder_pair_terms(self._h, ctypes.byref(n), None, None, None))
+        first = np.zeros(max(n.value, 1), np.uint32)
+        second = np.zeros(max(n.value, 1), np.uint32)
+        count = np.zeros(max(n.value, 1), np.int64)
+        check(lib().di_index_builder_pair_terms(self._h, ctypes.byref(n), ptr(first), ptr(second),
+                                                ptr(count)))
+        return first[:n.value], second[:n.value], count[:n.value]
 
     def info(self):
         nd, npairs = I64(), I64()
@@ -1017,3 +1098,22 @@ def write_reference_index(out_dir, table: TermTable, term_row, n_rows, term_off,
                                          ptr(term_row if term_row.size else one), int(n_rows),
                                          ptr(term_off), ptr(pdoc if pdoc.size else one),
                                          ptr(pval if pval.size else one)))
+
+
+def write_reference_index_pairwise(out_dir, table: TermTable, first_id, second_id, term_row,
+                                   n_rows, term_off, pdoc, pval):
+    """di_write_reference_index_pairwise: write_reference_index with the pair terms of
+    IndexBuilder.pair_terms, term_row as TermTable.rows_pairwise numbers them."""
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+    first_id = np.ascontiguousarray(first_id, np.uint32)
+    second_id = np.ascontiguousarray(second_id, np.uint32)
+    term_row = np.ascontiguousarray(term_row, np.int32)
+    term_off = np.ascontiguousarray(term_off, np.int64)
+    pdoc = np.ascontiguousarray(pdoc, np.uint32)
+    pval = np.ascontiguousarray(pval, np.uint8)
+    one = np.zeros(1, np.int32)
+    check(lib().di_write_reference_index_pairwise(
+        str(out_dir).encode("utf-8"), table._h, first_id.size,
+        ptr(first_id if first_id.size else one), ptr(second_id if second_id.size else one),
+        ptr(term_row if term_row.size else one), int(n_rows), ptr(term_off),
+        ptr(pdoc if pdoc.size else one), ptr(pval if pval.size else one)))

@@ -59,6 +59,50 @@ void check_term(std::string_view x, int64_t i) {
                (long long)i, (int)std::min<size_t>(x.size(), 200), x.data(), why);
 }
 
+// The names of the entries of di_term_table_rows_pairwise, compared without being built:
+// entry e < n_terms is term e, entry n_terms + u is term[first[u]] + '|' + term[second[u]].
+struct PairNames {
+    const di_term_table *t;
+    const uint32_t *first, *second;
+    size_t n_terms;
+    static constexpr std::string_view kBar{"|", 1};
+
+    int parts(uint64_t e, std::string_view out[3]) const {
+        if (e < n_terms) {
+            out[0] = t->terms[(size_t)e];
+            return 1;
+        }
+        out[0] = t->terms[first[e - n_terms]];
+        out[1] = kBar;
+        out[2] = t->terms[second[e - n_terms]];
+        return 3;
+    }
+    // < 0, 0, > 0 as unsigned bytes: code-point order for valid UTF-8
+    int compare(uint64_t a, uint64_t b) const {
+        std::string_view pa[3], pb[3];
+        const int na = parts(a, pa), nb = parts(b, pb);
+        int ia = 0, ib = 0;
+        size_t oa = 0, ob = 0;
+        for (;;) {
+            while (ia < na && oa == pa[ia].size()) ++ia, oa = 0;
+            while (ib < nb && ob == pb[ib].size()) ++ib, ob = 0;
+            if (ia == na || ib == nb) return (ia == na ? 0 : 1) - (ib == nb ? 0 : 1);
+            const size_t n = std::min(pa[ia].size() - oa, pb[ib].size() - ob);
+            const int c = std::memcmp(pa[ia].data() + oa, pb[ib].data() + ob, n);
+            if (c) return c;
+            oa += n;
+            ob += n;
+        }
+    }
+    std::string name(uint64_t e) const {
+        std::string_view p[3];
+        const int n = parts(e, p);
+        std::string s;
+        for (int i = 0; i < n; ++i) s.append(p[i].data(), p[i].size());
+        return s;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -134,6 +178,67 @@ int di_term_table_rows(const di_term_table *t, const int64_t *term_count, int32_
                   [&](uint32_t a, uint32_t b) { return t->terms[a] < t->terms[b]; });
         for (size_t r = 0; r < kept.size(); ++r) term_row[kept[r]] = (int32_t)r;
         *n_rows = (int64_t)kept.size();
+    });
+}
+
+int di_term_table_rows_pairwise(const di_term_table *t, const int64_t *term_count,
+                                int64_t n_pair_terms, const uint32_t *first_id,
+                                const uint32_t *second_id, int32_t *term_row, int64_t *n_rows) {
+    return guard([&] {
+        DI_REQUIRE(t && n_rows && n_pair_terms >= 0 && term_row &&
+                       (t->terms.empty() || term_count) &&
+                       (n_pair_terms == 0 || (first_id && second_id)),
+                   DI_EINVAL, "bad argument");
+        const size_t n_terms = t->terms.size();
+        for (int64_t u = 0; u < n_pair_terms; ++u)
+            DI_REQUIRE(first_id[u] < n_terms && second_id[u] < n_terms, DI_EINVAL,
+                       "pair %lld: a term id is not below n_terms = %lld", (long long)u,
+                       (long long)n_terms);
+        // an entry: a single term id, or n_terms + u
+        std::vector<uint64_t> single, pairs((size_t)n_pair_terms);
+        for (size_t i = 0; i < n_terms; ++i) {
+            term_row[i] = -1;
+            if (term_count[i] > 0) single.push_back(i);
+        }
+        for (int64_t u = 0; u < n_pair_terms; ++u) {
+            term_row[n_terms + (size_t)u] = -1;
+            pairs[(size_t)u] = n_terms + (uint64_t)u;
+        }
+        DI_REQUIRE(single.size() + pairs.size() <= (size_t)INT32_MAX, DI_ERANGE,
+                   "more than 2^31 kept terms");
+        const PairNames names{t, first_id, second_id, n_terms};
+        auto less = [&](uint64_t a, uint64_t b) { return names.compare(a, b) < 0; };
+        std::sort(single.begin(), single.end(), less);
+        // the pair names: sorted in contiguous chunks on the host threads, then merged
+        const int64_t P = n_pair_terms;
+        const int C = (int)std::min<int64_t>(host_threads(), std::max<int64_t>(P / 4096, 1));
+        parallel_for_threads(C, C, [&](int64_t lo, int64_t hi, int) {
+            for (int64_t c = lo; c < hi; ++c)
+                std::sort(pairs.begin() + P * c / C, pairs.begin() + P * (c + 1) / C, less);
+        });
+        for (int w = 1; w < C; w *= 2) {
+            const int merges = (C + 2 * w - 1) / (2 * w);
+            parallel_for_threads(merges, merges, [&](int64_t lo, int64_t hi, int) {
+                for (int64_t g = lo; g < hi; ++g) {
+                    const int a = (int)g * 2 * w, m = std::min(a + w, C), e = std::min(a + 2 * w, C);
+                    std::inplace_merge(pairs.begin() + P * a / C, pairs.begin() + P * m / C,
+                                       pairs.begin() + P * e / C, less);
+                }
+            });
+        }
+        std::vector<uint64_t> all(single.size() + pairs.size());
+        std::merge(single.begin(), single.end(), pairs.begin(), pairs.end(), all.begin(), less);
+        for (size_t r = 0; r + 1 < all.size(); ++r)
+            if (names.compare(all[r], all[r + 1]) == 0) {
+                const std::string x = names.name(all[r]);
+                DI_REQUIRE(false, DI_EFORMAT,
+                           "two kept terms are named '%.200s' (a pair name equals another "
+                           "entry's): the text route merges them into one vocabulary line; build "
+                           "this collection by the text route (index, quantize, inverted_index)",
+                           x.c_str());
+            }
+        for (size_t r = 0; r < all.size(); ++r) term_row[all[r]] = (int32_t)r;
+        *n_rows = (int64_t)all.size();
     });
 }
 

@@ -314,40 +314,78 @@ extern "C" int di_build_reference_index(const char *collection_path, const char 
 }
 
 // The same three files from the CSR di_index_builder_postings returns (rows already in
-// vocab.txt order, postings in file order) and the table that numbered the terms.
+// vocab.txt order, postings in file order) and the table that numbered the terms; pair
+// term u (term id n_terms + u) is named term[first_id[u]] + '|' + term[second_id[u]].
+static void write_builder_index(const char *out_dir, const di_term_table *table,
+                                int64_t n_pair_terms, const uint32_t *first_id,
+                                const uint32_t *second_id, const int32_t *term_row,
+                                int64_t n_rows, const int64_t *term_off, const uint32_t *pdoc,
+                                const uint8_t *pval) {
+    DI_REQUIRE(out_dir && table && term_off && n_rows >= 0 && n_pair_terms >= 0, DI_EINVAL,
+               "null argument");
+    DI_REQUIRE((table->terms.empty() && n_pair_terms == 0) || term_row, DI_EINVAL,
+               "null term_row");
+    DI_REQUIRE(n_pair_terms == 0 || (first_id && second_id), DI_EINVAL, "null pair ids");
+    const size_t n_terms = table->terms.size();
+    std::vector<std::string> pair_name((size_t)n_pair_terms);
+    std::vector<std::string_view> vocab((size_t)n_rows);
+    std::vector<uint8_t> seen((size_t)n_rows, 0);
+    for (size_t t = 0; t < n_terms + (size_t)n_pair_terms; ++t) {
+        const int64_t r = term_row[t];
+        if (r < 0) continue;
+        DI_REQUIRE(r < n_rows && !seen[(size_t)r], DI_EINVAL,
+                   "term id %lld: row %lld is out of range or given twice", (long long)t,
+                   (long long)r);
+        seen[(size_t)r] = 1;
+        if (t < n_terms) {
+            vocab[(size_t)r] = table->terms[t];
+            continue;
+        }
+        const size_t u = t - n_terms;
+        DI_REQUIRE(first_id[u] < n_terms && second_id[u] < n_terms, DI_EINVAL,
+                   "pair %lld: a term id is not below n_terms = %lld", (long long)u,
+                   (long long)n_terms);
+        std::string &x = pair_name[u];
+        x.reserve(table->terms[first_id[u]].size() + 1 + table->terms[second_id[u]].size());
+        x.append(table->terms[first_id[u]]).append("|").append(table->terms[second_id[u]]);
+        vocab[(size_t)r] = x;
+    }
+    for (int64_t r = 0; r < n_rows; ++r) {
+        DI_REQUIRE(seen[(size_t)r], DI_EINVAL, "row %lld has no term", (long long)r);
+        DI_REQUIRE(term_off[r + 1] >= term_off[r] && term_off[0] == 0, DI_EINVAL,
+                   "term_off not monotone at %lld", (long long)r);
+    }
+    const int64_t n = n_rows ? term_off[n_rows] : 0;
+    DI_REQUIRE(n == 0 || (pdoc && pval), DI_EINVAL, "null postings");
+    std::vector<unsigned char> dat((size_t)n * 5);
+    parallel_for(n, [&](int64_t lo, int64_t hi, int) {
+        for (int64_t i = lo; i < hi; ++i) {
+            std::memcpy(&dat[(size_t)i * 5], &pdoc[i], 4);
+            dat[(size_t)i * 5 + 4] = pval[i];
+        }
+    });
+    write_reference_files(out_dir, vocab, term_off, dat.data());
+}
+
 extern "C" int di_write_reference_index(const char *out_dir, const di_term_table *table,
                                         const int32_t *term_row, int64_t n_rows,
                                         const int64_t *term_off, const uint32_t *pdoc,
                                         const uint8_t *pval) {
     return guard([&] {
-        DI_REQUIRE(out_dir && table && term_off && n_rows >= 0, DI_EINVAL, "null argument");
-        DI_REQUIRE(table->terms.empty() || term_row, DI_EINVAL, "null term_row");
-        std::vector<std::string_view> vocab((size_t)n_rows);
-        std::vector<uint8_t> seen((size_t)n_rows, 0);
-        for (size_t t = 0; t < table->terms.size(); ++t) {
-            const int64_t r = term_row[t];
-            if (r < 0) continue;
-            DI_REQUIRE(r < n_rows && !seen[(size_t)r], DI_EINVAL,
-                       "term id %lld: row %lld is out of range or given twice", (long long)t,
-                       (long long)r);
-            seen[(size_t)r] = 1;
-            vocab[(size_t)r] = table->terms[t];
-        }
-        for (int64_t r = 0; r < n_rows; ++r) {
-            DI_REQUIRE(seen[(size_t)r], DI_EINVAL, "row %lld has no term", (long long)r);
-            DI_REQUIRE(term_off[r + 1] >= term_off[r] && term_off[0] == 0, DI_EINVAL,
-                       "term_off not monotone at %lld", (long long)r);
-        }
-        const int64_t n = n_rows ? term_off[n_rows] : 0;
-        DI_REQUIRE(n == 0 || (pdoc && pval), DI_EINVAL, "null postings");
-        std::vector<unsigned char> dat((size_t)n * 5);
-        parallel_for(n, [&](int64_t lo, int64_t hi, int) {
-            for (int64_t i = lo; i < hi; ++i) {
-                std::memcpy(&dat[(size_t)i * 5], &pdoc[i], 4);
-                dat[(size_t)i * 5 + 4] = pval[i];
-            }
-        });
-        write_reference_files(out_dir, vocab, term_off, dat.data());
+        write_builder_index(out_dir, table, 0, nullptr, nullptr, term_row, n_rows, term_off, pdoc,
+                            pval);
+    });
+}
+
+extern "C" int di_write_reference_index_pairwise(const char *out_dir, const di_term_table *table,
+                                                 int64_t n_pair_terms, const uint32_t *first_id,
+                                                 const uint32_t *second_id,
+                                                 const int32_t *term_row, int64_t n_rows,
+                                                 const int64_t *term_off, const uint32_t *pdoc,
+                                                 const uint8_t *pval) {
+    return guard([&] {
+        write_builder_index(out_dir, table, n_pair_terms, first_id, second_id, term_row, n_rows,
+                            term_off, pdoc, pval);
     });
 }
 

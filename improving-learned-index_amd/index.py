@@ -16,7 +16,10 @@ inverted_index.dat) in DIR in the same process, from the encoder's device output
 of `quantize` and `inverted_index` run over the impact TSV, without that file (--max_val:
 quantize's -m; --output_file_path is then optional and still writes the TSV).  One GPU:
 not with --pairwise, --doc_range or more than one rank.  DI_INDEX_TEXT_ROUTE=1 runs the
-three text steps into DIR instead (A/B).
+three text steps into DIR instead (A/B).  The device route itself takes the pairwise model
+-- run(..., pairwise=True, inverted_index_path=DIR) and Indexer.build_index build the
+'t1|t2' postings on the GPU -- but the command line still refuses the combination; that
+switch is a follow-up, as is DI_INDEX_TEXT_ROUTE for it.
 Multi-GPU: --doc_range start:end encodes one doc-id shard; concatenating the
 shard outputs in order gives the single-GPU file.  Under torchrun
 (--nproc-per-node N) every rank encodes doc-id shard r on its GPU and rank 0 joins
@@ -50,7 +53,8 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
         max_val=None):
     """inverted_index_path: build the quantized index there on the device
     (Indexer.build_index's route) instead of / beside the impact TSV; output_file_path may
-    then be None."""
+    then be None.  With pairwise=True the pair scores stay on the device too and the index
+    holds the 't1|t2' terms (IndexBuilder.append_pairwise)."""
     # --pairwise: DeepPairwiseImpact through the same Indexer (its lines add the
     # 't1|t2' entries and are sorted by score, pairwise_impact.py:98-129)
     model_cls = DeepPairwiseImpact if pairwise else DeepImpact
@@ -149,8 +153,10 @@ ONE_GPU = ("--inverted_index_path builds the index on one GPU: pass --device or 
 def _check_index_route(p, a):
     """--inverted_index_path: one process, the whole collection, the single-term model."""
     if a.pairwise:
-        p.error("--inverted_index_path does not take --pairwise: the pairwise collection goes "
-                "through the text route (index, quantize, inverted_index)")
+        p.error("--inverted_index_path does not take --pairwise on the command line yet: call "
+                "index.run(..., pairwise=True, inverted_index_path=DIR) or "
+                "Indexer.build_index, or go through the text route (index, quantize, "
+                "inverted_index)")
     if a.doc_range is not None:
         p.error("--inverted_index_path does not take --doc_range. " + ONE_GPU)
     if parallel.dist_env()[0] > 1 or (a.device is None and parallel.ranks_to_spawn(a.gpus) > 1):

@@ -121,6 +121,34 @@ class TokenizerPool:
 
 
 DEVICE_DOCS = 4096  # documents per device call when tokenizer chunks are merged
+PAIR_STEP_T2 = 1 << 32  # di_encode_pairwise: the sum of T_d^2 over the documents of a call
+
+
+def _slice_packed_blob(packed, lo, hi):
+    """Documents [lo, hi) of a pack_processed_blob batch, as such a batch."""
+    ids, cu, blob, term_off, tt, ct = packed
+    t0, t1 = int(ct[lo]), int(ct[hi])
+    return (ids[cu[lo]:cu[hi]], (cu[lo:hi + 1] - cu[lo]).astype(cu.dtype),
+            blob[int(term_off[t0]):int(term_off[t1])],
+            (term_off[t0:t1 + 1] - term_off[t0]).astype(term_off.dtype), tt[t0:t1],
+            (ct[lo:hi + 1] - ct[lo]).astype(ct.dtype))
+
+
+def _pair_step_ranges(ct, budget):
+    """[lo, hi) document ranges of a batch whose sums of T_d^2 stay within `budget` (a
+    document over it alone gets a range of its own: the library refuses it)."""
+    import numpy as np
+
+    t2 = np.diff(np.asarray(ct, np.int64)) ** 2
+    out, lo, run = [], 0, 0
+    for d, x in enumerate(t2.tolist()):
+        if d > lo and run + x > budget:
+            out.append((lo, d))
+            lo, run = d, 0
+        run += x
+    if len(t2) > lo:
+        out.append((lo, len(t2)))
+    return out
 
 
 class _Writer:
@@ -272,7 +300,9 @@ class Indexer:
         same collection, without its files.  The round3 impacts of every device step stay
         on the GPU and go to an IndexBuilder; the terms are numbered by a TermTable from
         the tokenizer's blob.  documents_or_batches: a sequence of passages, or an iterable
-        of such batches (document ids count on across them).  max_val: quantize's -m.
+        of such batches (document ids count on across them).  A DeepPairwiseImpact model
+        gives the index of index --pairwise -> quantize -> inverted_index, 't1|t2' terms
+        included.  max_val: quantize's -m.
         index_path: also write vocab.txt / inverted_index.idx / inverted_index.dat there.
         file: also write the impact TSV there, from the same encode."""
         docs = documents_or_batches
@@ -296,15 +326,20 @@ class IndexBuild:
     """The device route from documents to the quantized index, one batch at a time: the
     submit / finish protocol of Indexer (so index.py's loop drives either), the impacts
     appended to an IndexBuilder instead of formatted -- and formatted as well when the
-    impact TSV is wanted (write_tsv: the bytes of Indexer.index)."""
+    impact TSV is wanted (write_tsv: the bytes of Indexer.index).  With a
+    DeepPairwiseImpact the pair scores stay on the device as well (_pair_step) and the
+    index holds the 't1|t2' terms; its bf16 precision is refused, as in the encoder."""
 
     def __init__(self, indexer: "Indexer", write_tsv: bool = True):
         from .models import DeepPairwiseImpact
 
         model = indexer.model
-        if isinstance(model, DeepPairwiseImpact) or not hasattr(model, "encoder"):
-            raise ValueError("the device index route needs a DeepImpact model on a DeviceEncoder "
-                             "(the pairwise collection goes through the text route)")
+        if not hasattr(model, "encoder"):
+            raise ValueError("the device index route needs a DeepImpact or DeepPairwiseImpact "
+                             "model on a DeviceEncoder")
+        self.pairwise = isinstance(model, DeepPairwiseImpact)
+        if self.pairwise and getattr(model.encoder, "precision", None) == "bf16":
+            raise ValueError("DeepPairwiseImpact runs at fp32 or bf16x3")
         self.indexer, self.model, self.write_tsv = indexer, model, write_tsv
         self.device = getattr(model.encoder, "device", 0) or 0
         self.table = _lib.TermTable()
@@ -346,6 +381,9 @@ class IndexBuild:
         import numpy as np
         import torch
 
+        if self.pairwise:
+            return "".join(self._pair_step(_slice_packed_blob(packed, lo, hi))
+                           for lo, hi in _pair_step_ranges(packed[5], PAIR_STEP_T2))
         ids, cu, blob, term_off, tt, ct = packed
         t0 = time.perf_counter()
         dev = torch.device("cuda", self.device)
@@ -368,6 +406,67 @@ class IndexBuild:
         text = ""
         if self.write_tsv:
             text = _lib.format_impact_lines_packed(blob, term_off, d_imp[:n_terms].cpu().numpy(), ct)
+        t3 = time.perf_counter()
+        self.ms["encode"] += (t2 - t1) * 1e3
+        self.ms["build"] += (t1 - t0 + t3 - t2) * 1e3
+        return text
+
+    def _pair_step(self, packed) -> str:
+        """One device step of the pairwise model: the unrounded single and pair scores of
+        encode_pairwise stay in torch buffers and go to the builder (which rounds them);
+        for the TSV the same buffers are ordered on the device (di_pairwise_order, round3)
+        and only the entries come to the host."""
+        import time
+
+        import numpy as np
+        import torch
+
+        ids, cu, blob, term_off, tt, ct = packed
+        t0 = time.perf_counter()
+        dev = torch.device("cuda", self.device)
+        n_docs, n_terms = len(cu) - 1, int(ct[-1])
+        tid = self.table.intern(blob, term_off).view(np.int32)
+        tt, ct = np.asarray(tt, np.int32)[:n_terms], np.ascontiguousarray(ct, np.int32)
+        T = np.diff(ct.astype(np.int64))
+        cu_pairs = np.zeros(n_docs + 1, np.int64)
+        cu_pairs[1:] = np.cumsum(T * (T - 1) // 2)
+        n_pairs = int(cu_pairs[-1])
+        # the encoder and the builder take a document's terms in token order; the
+        # bert_legacy maps can differ from it (models._encode_entries_device)
+        asc = np.ones(n_terms, bool)
+        asc[1:] = tt[1:] > tt[:-1]
+        asc[ct[:-1][ct[:-1] < n_terms]] = True
+        by_tok = pos = None
+        if not asc.all():
+            tdoc = np.repeat(np.arange(n_docs), T)
+            by_tok = np.lexsort((tt, tdoc))
+            pos = (by_tok - ct[tdoc]).astype(np.int32)
+            tt, tid = tt[by_tok], tid[by_tok]
+        pad = lambda a, dt=np.int32: a if a.size else np.zeros(1, dt)  # noqa: E731
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        d_ids, d_cu = up(pad(np.ascontiguousarray(ids, np.int32))), up(np.asarray(cu, np.int32))
+        d_tt, d_ct, d_tid, d_cup = up(pad(tt)), up(ct), up(pad(tid)), up(cu_pairs)
+        d_single = torch.empty(max(1, n_terms), dtype=torch.float32, device=dev)[:n_terms]
+        d_pair = torch.empty(max(1, n_pairs), dtype=torch.float32, device=dev)[:n_pairs]
+        t1 = time.perf_counter()
+        # synchronous at return (no DI_F_ASYNC): the builder's stream may read the buffers
+        self.model.encoder.encode_pairwise_device(
+            d_ids, d_cu, n_docs, int(cu[-1]), int(np.diff(cu).max(initial=0)), d_tt, d_ct,
+            n_terms, d_cup, n_pairs, d_single, d_pair, None, flags=_lib.DI_F_DEVICE_PTRS)
+        t2 = time.perf_counter()
+        self.builder.append_pairwise(d_tid, d_single, d_pair, d_ct, d_cup, timing=True)
+        text = ""
+        if self.write_tsv:
+            d_pos = up(pos) if pos is not None else None
+            cu_out, first, second, score = _lib.pairwise_order(
+                d_single, d_pair, d_ct, d_cup, d_pos, round3=True, device=self.device)
+            cu_out, first = cu_out.cpu().numpy(), first.cpu().numpy()
+            second, score = second.cpu().numpy(), score.cpu().numpy()
+            if by_tok is not None:  # sorted-term indices back to the blob's (map) order
+                by32 = by_tok.astype(np.int32)
+                first, second = by32[first], np.where(second >= 0, by32[np.maximum(second, 0)],
+                                                      np.int32(-1)).astype(np.int32)
+            text = _lib.format_entry_lines(blob, term_off, first, second, score, cu_out)
         t3 = time.perf_counter()
         self.ms["encode"] += (t2 - t1) * 1e3
         self.ms["build"] += (t1 - t0 + t3 - t2) * 1e3

@@ -55,17 +55,26 @@ class InvertedIndex:
         object as InvertedIndex(path) over the files the text route writes for the same
         collection.  The builder's postings come back in file order (sorted on the GPU) and
         go through di_index_create; ``vocab`` is the table's terms that kept a posting, in
-        sorted() order.  index_path: also write vocab.txt / inverted_index.idx /
+        sorted() order -- with the 't1|t2' terms of a builder filled by append_pairwise
+        among them.  index_path: also write vocab.txt / inverted_index.idx /
         inverted_index.dat there."""
         if getattr(builder, "term_count", None) is None:
             raise ValueError("IndexBuilder.quantize comes first")
-        term_row, n_rows = table.rows(builder.term_count)
+        first_id, second_id, _ = builder.pair_terms()
+        if first_id.size:  # a pairwise builder: the rows of the 'a|b' terms as well
+            term_row, n_rows = table.rows_pairwise(builder.term_count, first_id, second_id)
+        else:
+            term_row, n_rows = table.rows(builder.term_count)
         term_off, pdoc, pval = builder.postings(term_row, n_rows, timing=timing)
-        if index_path is not None:
+        if index_path is not None and first_id.size:
+            _lib.write_reference_index_pairwise(index_path, table, first_id, second_id, term_row,
+                                                n_rows, term_off, pdoc, pval)
+        elif index_path is not None:
             _lib.write_reference_index(index_path, table, term_row, n_rows, term_off, pdoc, pval)
         self = cls.__new__(cls)
         self.index_path = Path(index_path) if index_path is not None else None
-        self.vocab = table.vocab(term_row)
+        self.vocab = (table.vocab(term_row, first_id, second_id) if first_id.size
+                      else table.vocab(term_row))
         self.device = builder.device if device is None else device
         self.doc_lo, self.doc_hi = doc_lo, doc_hi
         self._dev = DeviceIndex.from_postings(term_off, pdoc, pval, doc_lo, doc_hi, self.device)

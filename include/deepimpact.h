@@ -289,6 +289,19 @@ int di_term_table_export(const di_term_table *t, char *blob, int64_t *term_off);
  * and -1 for every other term; *n_rows = the terms that have a row. */
 int di_term_table_rows(const di_term_table *t, const int64_t *term_count, int32_t *term_row,
                        int64_t *n_rows);
+/* di_term_table_rows over the single terms and the pair terms of
+ * di_index_builder_pair_terms: term_row[id] for the n_terms ids of the table, then
+ * term_row[n_terms + u] for pair u, whose name is term[first_id[u]] + '|' +
+ * term[second_id[u]] (pairwise_impact.py:120-124); rows = sorted() over the UTF-8 bytes of
+ * every single term with term_count > 0 and every pair name (the pair names are sorted on
+ * DI_HOST_THREADS threads).  Two entries with the same name -- a single term 'x|y' beside
+ * the pair ('x', 'y'), or ('x|y', 'z') beside ('x', 'y|z') -- are DI_EFORMAT naming the
+ * term: the text route merges them into one vocabulary line (create.py:24-41), this route
+ * does not, so build such a collection by the text route.  An id of a pair not below
+ * n_terms: DI_EINVAL; more than 2^31 - 1 rows: DI_ERANGE. */
+int di_term_table_rows_pairwise(const di_term_table *t, const int64_t *term_count,
+                                int64_t n_pair_terms, const uint32_t *first_id,
+                                const uint32_t *second_id, int32_t *term_row, int64_t *n_rows);
 int di_term_table_destroy(di_term_table *t);
 
 /* ---- device builder: documents as (term id, impact) pairs, e.g. di_encode's device
@@ -313,6 +326,31 @@ int di_index_builder_reserve(di_index_builder *b, int64_t n_docs, int64_t n_pair
 int di_index_builder_append(di_index_builder *b, const uint32_t *term_ids, const float *impacts,
                             const int32_t *cu_terms, int32_t n_docs, int64_t *first_doc,
                             void *hip_stream, uint32_t flags);
+/* Appends n_docs documents of the pairwise model (DeepPairwiseImpact.compute_term_impacts,
+ * pairwise_impact.py:98-129) from di_encode_pairwise's unrounded outputs: term_ids,
+ * single (n_terms entries) and cu_terms as di_index_builder_append takes them, the terms in
+ * token order inside a document; pair[n_pairs] and cu_pairs (int64) the pair scores, pair
+ * j of a T-term document d being the combination (a < b) at
+ * cu_pairs[d] + a(2T - a - 1)/2 + (b - a - 1).  The call applies DI_F_ROUND3's round3 to
+ * both.  The singles are appended as di_index_builder_append appends their rounded values;
+ * a pair is kept iff its rounded score is not zero (:122) and becomes one record
+ * (id(t_a), id(t_b), doc, rounded score), 16 bytes, in document order -- the posting of the
+ * term t_a + '|' + t_b (:120-124), whose identity is the pair of ids.  Placement is by
+ * tile counts, a scan and ballots: no atomic hands out a slot.  n_pairs of
+ * di_index_builder_info counts the singles only.  With DI_F_DEVICE_PTRS the five arrays
+ * are device pointers and only cu_terms and cu_pairs are read back.  Runs on hip_stream
+ * and waits for it.  cu_terms or cu_pairs not starting at 0 or decreasing, cu_pairs not
+ * ending at n_pairs, or a document with cu_pairs[d + 1] - cu_pairs[d] != T(T - 1)/2:
+ * DI_EINVAL; more than 2^32 - 1 documents in all: DI_ERANGE; a document without terms is
+ * remembered (DI_EFORMAT at quantize) and a non-finite score is reported at quantize, as
+ * for di_index_builder_append.  After an error the builder is as it was before the call.
+ * An append discards the result of an earlier quantize.  The pair buffers grow by
+ * reallocation.  DI_F_TIMING: "ib_append", "ib_pair_append", "ib_scan". */
+int di_index_builder_append_pairwise(di_index_builder *b, const uint32_t *term_ids,
+                                     const float *single, const float *pair,
+                                     const int32_t *cu_terms, const int64_t *cu_pairs,
+                                     int32_t n_docs, int64_t n_pairs, int64_t *first_doc,
+                                     void *hip_stream, uint32_t flags);
 int di_index_builder_info(const di_index_builder *b, int64_t *n_docs, int64_t *n_pairs);
 /* quantize_file (quantize.py:13-47) on everything appended: max_val <= 0 means the
  * maximum over all pairs, starting from 0 (:17-24); scale = 255 / max_val in fp64;
@@ -326,10 +364,26 @@ int di_index_builder_info(const di_index_builder *b, int64_t *n_docs, int64_t *n
  * error word read once per step).  After an error the builder is as it was before the
  * call, the result of an earlier quantize included.  May be called again with another
  * max_val: the float impacts stay.  Runs on hip_stream and waits for it.
- * DI_F_TIMING: "ib_quantize", "ib_scan", "ib_compact". */
+ * DI_F_TIMING: "ib_quantize", "ib_scan", "ib_compact".
+ * On a builder that holds pair records (di_index_builder_append_pairwise) the maximum
+ * runs over singles and pairs, the pair records are quantized by the same arithmetic
+ * with the same errors (either id >= n_terms: DI_EINVAL), and the kept ones are numbered:
+ * a stable radix sort by the key (id_a << 32) | id_b (ceil(bits(n_terms - 1) / 8) passes a
+ * half, so a key's records stay in ascending doc order), run heads flagged and scanned,
+ * pair number u = the rank of the distinct key.  Pair u is term id n_terms + u of the kept
+ * records: *n_kept counts singles and pairs, di_index_builder_postings then takes
+ * term_row[n_terms + n_pair_terms], and di_index_builder_pair_terms gives the keys.
+ * n_terms + n_pair_terms above 2^31 - 1: DI_ERANGE.  DI_F_TIMING adds "ib_pair_quantize",
+ * "ib_pair_compact", "ib_pair_hist", "ib_pair_scatter", "ib_pair_number". */
 int di_index_builder_quantize(di_index_builder *b, int64_t n_terms, double max_val,
                               void *hip_stream, uint32_t flags, double *max_used,
                               int64_t *term_count, int64_t *n_kept);
+/* The distinct pair keys that kept a posting in the last quantize, in ascending order of
+ * (first_id, second_id), and their kept postings: *n_pair_terms, and first_id, second_id,
+ * count [n_pair_terms] (host; any of the three may be NULL, e.g. to ask for the size).
+ * Before a quantize: DI_EINVAL. */
+int di_index_builder_pair_terms(const di_index_builder *b, int64_t *n_pair_terms,
+                                uint32_t *first_id, uint32_t *second_id, int64_t *count);
 /* The kept postings in the reference file order -- row-major by term_row (host,
  * n_terms entries, -1 = no row), value descending, doc ascending (create.py:41, a stable
  * sort of a doc-ordered list) -- as the input of di_index_create: term_off[n_rows + 1],
@@ -350,6 +404,15 @@ int di_index_builder_destroy(di_index_builder *b);
 int di_write_reference_index(const char *out_dir, const di_term_table *table,
                              const int32_t *term_row, int64_t n_rows, const int64_t *term_off,
                              const uint32_t *pdoc, const uint8_t *pval);
+/* The same with pair terms: term_row[n_terms + n_pair_terms] as
+ * di_term_table_rows_pairwise numbers them, and pair u's line of vocab.txt is
+ * term[first_id[u]] + '|' + term[second_id[u]].  A row out of range, given twice or
+ * without a term, or a pair id not below n_terms: DI_EINVAL. */
+int di_write_reference_index_pairwise(const char *out_dir, const di_term_table *table,
+                                      int64_t n_pair_terms, const uint32_t *first_id,
+                                      const uint32_t *second_id, const int32_t *term_row,
+                                      int64_t n_rows, const int64_t *term_off,
+                                      const uint32_t *pdoc, const uint8_t *pval);
 
 /* ======================================================================
  * Encoder: DeepImpact forward + first-occurrence gather     (A2, A5-A9)
