@@ -23,6 +23,8 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import DI_SHORT_QUERY_TERMS  # (a constant: the library itself loads on first use)
+
 
 def dist_env() -> Tuple[int, int, int]:
     """(world, rank, local_rank) from the torchrun environment (1, 0, 0 without it)."""
@@ -267,7 +269,7 @@ def decode_quant_keys(keys: np.ndarray, n: int, n_terms: int = 0) -> List[Tuple[
         raise RuntimeError("DI_ERANGE: the scorer rejected a query (out_n = -1: more than "
                            "DI_MAX_QUERY_TERMS terms, or a long query on a shard past doc 2^24)")
     k = keys[:n].astype(np.uint64)
-    wide = n_terms > 256  # DI_SHORT_QUERY_TERMS
+    wide = n_terms > DI_SHORT_QUERY_TERMS
     m, sh = (np.uint64(0xFFFFFF), np.uint64(44)) if wide else (np.uint64(0xFFFFFFFF), np.uint64(48))
     docs = (m - (k & m)).astype(np.int64)
     scores = (k >> sh).astype(np.int64)
@@ -282,7 +284,7 @@ def decode_quant_key_arrays(keys: np.ndarray, counts: np.ndarray, n_terms) -> Tu
     if counts.size and int(counts.min()) < 0:
         decode_quant_keys(keys[0], int(counts.min()))  # (raises the same error)
     k = keys.astype(np.uint64)
-    wide = (np.asarray(n_terms, np.int64) > 256)[:, None]  # DI_SHORT_QUERY_TERMS
+    wide = (np.asarray(n_terms, np.int64) > DI_SHORT_QUERY_TERMS)[:, None]
     m = np.where(wide, np.uint64(0xFFFFFF), np.uint64(0xFFFFFFFF))
     sh = np.where(wide, np.uint64(44), np.uint64(48))
     docs = (m - (k & m)).astype(np.uint32)
@@ -536,7 +538,7 @@ class ShardedRetriever:
 
         res = self.local_search(queries)
         # local_search may drop terms (unknown words): it then returns the term counts it
-        # actually submitted, which decide the key layout (wide above 256 terms)
+        # actually submitted, which decide the key layout (wide above DI_SHORT_QUERY_TERMS)
         keys, counts = res[0], res[1]
         n_terms = res[2] if len(res) > 2 else [len(q) for q in queries]
         world = dist.get_world_size(self.group)

@@ -105,6 +105,8 @@ class Ranker:
             else:
                 docs, scores, n, _ = self.index.search_ids(
                     [self.index.term_ids(t) for t in terms], self.top_k)
+                if len(n) and int(n.min()) < 0:  # (raises: a query the scorer rejected)
+                    parallel.decode_quant_keys(docs[0], int(n.min()))
             if self.run_file is None:
                 continue
             if os.environ.get("DI_RANK_PY_WRITES") == "1":  # (the per-query form, A/B)

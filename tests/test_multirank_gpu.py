@@ -126,8 +126,9 @@ def test_rank_cli_two_ranks_equals_one():
                   extra_env={"DI_FORCE_DIST": "1"})
         _same_run((td / "rccl.tsv").read_text(), (td / "one.tsv").read_text())
         # ... with the pruned two-round exchange forced at one rank: its device branch
-        # (torch.topk over the samples, the pack / unpack scatters, the padded round-2
-        # all_gather over nccl) -- the code every multi-GPU retrieve of configs[2]/[3] runs
+        # (the di_xchg_* kernels of exchange.hip -- sample, count, offsets, pack, unpack --
+        # around the three all_gathers over nccl, the padded round 2 among them) -- the
+        # code every multi-GPU retrieve of configs[2]/[3] runs
         _torchrun("rank", args + ["--output_path", str(td / "rccl_pruned.tsv")], world=1,
                   extra_env={"DI_FORCE_DIST": "1", "DI_EXCHANGE": "pruned"})
         _same_run((td / "rccl_pruned.tsv").read_text(), (td / "one.tsv").read_text())
