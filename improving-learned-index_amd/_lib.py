@@ -85,6 +85,9 @@ SIGNATURES = {
     "di_version": (ctypes.c_int, []),
     "di_device_count": (ctypes.c_int, [P]),
     "di_index_create": (ctypes.c_int, [P, I64, P, P, U32, U32, ctypes.c_int, P]),
+    "di_index_create_device": (ctypes.c_int, [P, I64, P, P, U32, U32, ctypes.c_int, P, U32, P]),
+    "di_index_layout": (ctypes.c_int, [P, P, P, P, P]),
+    "di_index_export": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, P, P]),
     "di_index_load_reference": (ctypes.c_int, [ctypes.c_char_p, U32, U32, ctypes.c_int, P]),
     "di_build_reference_index": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p]),
     "di_index_search": (ctypes.c_int, [P, P, P, I32, I32, P, P, P, P, U32]),
@@ -360,16 +363,37 @@ class DeviceIndex(_TimedHandle):
         self._h = handle
 
     @classmethod
-    def from_postings(cls, term_off, pdoc, pval, doc_lo=0, doc_hi=0, device=0):
+    def from_postings(cls, term_off, pdoc, pval, doc_lo=0, doc_hi=0, device=0, layout="host",
+                      stream=0, timing=False):
+        """layout="host": di_index_create (the blocked layout built on host threads and
+        uploaded); "device": di_index_create_device (built on the GPU, the same bytes), which
+        also takes torch device tensors (IndexBuilder.postings(device=True)) as they are."""
+        if layout not in ("host", "device"):
+            raise ValueError(f"layout must be 'host' or 'device', not {layout!r}")
+        h = ctypes.c_void_p()
+        if _is_device(term_off):
+            if layout != "device":
+                raise ValueError("device tensors need layout='device'")
+            flags = DI_F_DEVICE_PTRS | (DI_F_TIMING if timing else 0)
+            check(lib().di_index_create_device(ptr(term_off), len(term_off) - 1, ptr(pdoc),
+                                               ptr(pval), doc_lo, doc_hi, device,
+                                               ctypes.c_void_p(stream or 0), flags,
+                                               ctypes.byref(h)))
+            return cls(h)
         term_off = np.ascontiguousarray(term_off, np.int64)
         pdoc = np.ascontiguousarray(pdoc, np.uint32)
         pval = np.ascontiguousarray(pval, np.uint8)
         if pdoc.size == 0:
             pdoc = np.zeros(1, np.uint32)
             pval = np.zeros(1, np.uint8)
-        h = ctypes.c_void_p()
-        check(lib().di_index_create(ptr(term_off), len(term_off) - 1, ptr(pdoc), ptr(pval),
-                                    doc_lo, doc_hi, device, ctypes.byref(h)))
+        if layout == "device":
+            check(lib().di_index_create_device(ptr(term_off), len(term_off) - 1, ptr(pdoc),
+                                               ptr(pval), doc_lo, doc_hi, device,
+                                               ctypes.c_void_p(stream or 0),
+                                               DI_F_TIMING if timing else 0, ctypes.byref(h)))
+        else:
+            check(lib().di_index_create(ptr(term_off), len(term_off) - 1, ptr(pdoc), ptr(pval),
+                                        doc_lo, doc_hi, device, ctypes.byref(h)))
         return cls(h)
 
     @classmethod
@@ -385,6 +409,31 @@ class DeviceIndex(_TimedHandle):
                                   ctypes.byref(nd), ctypes.byref(nb)))
         return {"n_terms": nt.value, "n_postings": npo.value, "n_docs": nd.value,
                 "n_blocks": nb.value}
+
+    def layout(self):
+        ne, nl, bd, hf = I64(), I64(), I32(), I32()
+        check(lib().di_index_layout(self._h, ctypes.byref(ne), ctypes.byref(nl),
+                                    ctypes.byref(bd), ctypes.byref(hf)))
+        return {"n_ent": ne.value, "n_long": nl.value, "block_docs": bd.value,
+                "has_flat": bool(hf.value)}
+
+    def export(self):
+        """di_index_export: the device layout on the host, a dict of numpy arrays (post,
+        post_flat -- None without the flat array --, tb_start, eblk, epos, seg, lid, wmeta,
+        emax, wmax), of an index from either layout route."""
+        i, lay = self.info(), self.layout()
+        np_, ne, nl = i["n_postings"], lay["n_ent"], lay["n_long"]
+        a = {"post": np.zeros(np_, np.uint32),
+             "post_flat": np.zeros(np_, np.uint32) if lay["has_flat"] else None,
+             "tb_start": np.zeros(i["n_terms"] + 1, np.uint32),
+             "eblk": np.zeros(ne, np.uint16), "epos": np.zeros(ne + 1, np.uint32),
+             "seg": np.zeros(8 * ne, np.uint16), "lid": np.zeros(ne, np.uint32),
+             "wmeta": np.zeros(128 * nl, np.uint16), "emax": np.zeros(ne, np.uint8),
+             "wmax": np.zeros(16 * nl, np.uint8)}
+        check(lib().di_index_export(self._h, *[ptr(a[k]) for k in (
+            "post", "post_flat", "tb_start", "eblk", "epos", "seg", "lid", "wmeta", "emax",
+            "wmax")]))
+        return a
 
     def search_csr(self, q_terms, cu_q, k, with_keys=False, timing=False):
         q_terms, cu_q, n_q, docs, scores, n, keys = _query_arrays(q_terms, cu_q, k, np.uint32,

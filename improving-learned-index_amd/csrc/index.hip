@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "di_common.h"
+#include "index_layout.h"
 #include "topk_common.h"
 
 namespace di {
@@ -2647,6 +2648,10 @@ void build_index(di_index *ix, const int64_t *term_off, int64_t n_terms, const u
 
 }  // namespace
 
+static_assert(IL_BLOCK_DOCS == MAX_BLOCK_DOCS && IL_WSEG == WSEG && IL_WLONG_MIN == WLONG_MIN &&
+                  IL_POST_X == POST_X,
+              "index_layout.h builds the layout this scorer reads");
+
 namespace di {
 // Kernels using more than 64 KiB of dynamic LDS must opt in, once per device.
 void enable_big_lds() {
@@ -2761,6 +2766,22 @@ void launch_merge(const uint64_t *keys, const int32_t *counts, int n_q, int n_li
 
 extern "C" {
 
+// A di_index on `device` with its stream and the environment's settings, nothing built.
+static std::unique_ptr<di_index> new_index(int device) {
+    std::unique_ptr<di_index> ix(new di_index());
+    ix->device = device;
+    DI_HIP(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
+    ix->own_stream = true;
+    enable_big_lds();
+    if (const char *ab = std::getenv("DI_PROFILE_ABLATE")) ix->ablate = std::atoi(ab);
+    if (const char *bo = std::getenv("DI_BLOCK_ORDER")) ix->block_order = bo[0] == '1';
+    if (const char *st = std::getenv("DI_SCORE_THRESHOLD"))  // (tested both ways)
+        ix->shared_thr = st[0] != '0' ? 1 : 0;
+    if (const char *e = std::getenv("DI_TQ_EVERY")) ix->tq_every = std::max(1, std::atoi(e));
+    if (const char *e = std::getenv("DI_TQ_FIRST")) ix->tq_first = std::max(0, std::atoi(e));
+    return ix;
+}
+
 int di_index_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pdoc,
                     const uint8_t *pval, uint32_t doc_lo, uint32_t doc_hi, int device,
                     di_index **out) {
@@ -2769,19 +2790,90 @@ int di_index_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pd
                    "null argument");
         check_device(device);
         DeviceScope ds(device);
-        std::unique_ptr<di_index> ix(new di_index());
-        ix->device = device;
-        DI_HIP(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-        ix->own_stream = true;
-        enable_big_lds();
-        if (const char *ab = std::getenv("DI_PROFILE_ABLATE")) ix->ablate = std::atoi(ab);
-        if (const char *bo = std::getenv("DI_BLOCK_ORDER")) ix->block_order = bo[0] == '1';
-        if (const char *st = std::getenv("DI_SCORE_THRESHOLD"))  // (tested both ways)
-            ix->shared_thr = st[0] != '0' ? 1 : 0;
-        if (const char *e = std::getenv("DI_TQ_EVERY")) ix->tq_every = std::max(1, std::atoi(e));
-        if (const char *e = std::getenv("DI_TQ_FIRST")) ix->tq_first = std::max(0, std::atoi(e));
+        std::unique_ptr<di_index> ix = new_index(device);
         build_index(ix.get(), term_off, n_terms, pdoc, pval, doc_lo, doc_hi);
         *out = ix.release();
+    });
+}
+
+int di_index_create_device(const int64_t *term_off, int64_t n_terms, const uint32_t *pdoc,
+                           const uint8_t *pval, uint32_t doc_lo, uint32_t doc_hi, int device,
+                           void *hip_stream, uint32_t flags, di_index **out) {
+    return guard([&] {
+        DI_REQUIRE(out, DI_EINVAL, "null output");
+        *out = nullptr;
+        DI_REQUIRE(term_off && (n_terms == 0 || (pdoc && pval)), DI_EINVAL, "null argument");
+        DI_REQUIRE(n_terms >= 0, DI_EINVAL, "n_terms < 0");
+        DI_REQUIRE(n_terms < (int64_t)0xFFFFFFFF, DI_ERANGE, "n_terms %lld >= 2^32",
+                   (long long)n_terms);
+        check_device(device);
+        DeviceScope ds(device);
+        const bool dev = flags & DI_F_DEVICE_PTRS, timing = flags & DI_F_TIMING;
+        hipStream_t s = (hipStream_t)hip_stream;
+        std::unique_ptr<di_index> ix = new_index(device);
+        DevBuf in_off, in_doc, in_val;
+        size_t n_in = 0;  // postings a host caller's arrays hold: [0, term_off[n_terms])
+        if (!dev) {       // (checked before anything is copied; the device checks again)
+            DI_REQUIRE(term_off[0] >= 0, DI_EINVAL, "term_off[0] < 0");
+            for (int64_t t = 0; t < n_terms; ++t)
+                DI_REQUIRE(term_off[t + 1] >= term_off[t], DI_EINVAL,
+                           "term_off not monotone at %lld", (long long)t);
+            n_in = (size_t)term_off[n_terms];
+        }
+        const int64_t *d_off = stage_in(term_off, (size_t)n_terms + 1, dev, in_off, s);
+        const uint32_t *d_doc = stage_in(pdoc, n_in, dev, in_doc, s);
+        const uint8_t *d_val = stage_in(pval, n_in, dev, in_val, s);
+        IndexLayout lay{&ix->post, &ix->post_flat, &ix->tb_start, &ix->eblk, &ix->epos,
+                        &ix->seg,  &ix->lid,       &ix->wmeta,    &ix->emax, &ix->wmax};
+        build_layout_device(d_off, n_terms, d_doc, d_val, doc_lo, doc_hi, s, timing, ix->timer,
+                            lay);
+        ix->n_terms = n_terms;
+        ix->n_post = lay.n_post;
+        ix->n_ent = lay.n_ent;
+        ix->n_long = lay.n_long;
+        ix->n_docs = lay.n_docs;
+        ix->doc_lo = lay.doc_lo;
+        ix->nb = lay.nb;
+        ix->block_docs = lay.block_docs;
+        ix->has_flat = lay.has_flat;
+        *out = ix.release();
+    });
+}
+
+int di_index_layout(const di_index *ix, int64_t *n_ent, int64_t *n_long, int32_t *block_docs,
+                    int32_t *has_flat) {
+    return guard([&] {
+        DI_REQUIRE(ix, DI_EINVAL, "null handle");
+        if (n_ent) *n_ent = ix->n_ent;
+        if (n_long) *n_long = ix->n_long;
+        if (block_docs) *block_docs = ix->block_docs;
+        if (has_flat) *has_flat = ix->has_flat ? 1 : 0;
+    });
+}
+
+int di_index_export(const di_index *ix, uint32_t *post, uint32_t *post_flat, uint32_t *tb_start,
+                    uint16_t *eblk, uint32_t *epos, uint16_t *seg, uint32_t *lid, uint16_t *wmeta,
+                    uint8_t *emax, uint8_t *wmax) {
+    return guard([&] {
+        DI_REQUIRE(ix, DI_EINVAL, "null handle");
+        DI_REQUIRE(!post_flat || ix->has_flat, DI_EINVAL,
+                   "no flat posting array (DI_DEAL_CLASSES=1 at create)");
+        DeviceScope ds(ix->device);
+        DI_HIP(hipStreamSynchronize(ix->stream));
+        auto get = [](void *dst, const DevBuf &b, size_t bytes) {
+            if (dst && bytes) DI_HIP(hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost));
+        };
+        const size_t np = (size_t)ix->n_post, ne = (size_t)ix->n_ent, nl = (size_t)ix->n_long;
+        get(post, ix->post, np * 4);
+        get(post_flat, ix->post_flat, np * 4);
+        get(tb_start, ix->tb_start, ((size_t)ix->n_terms + 1) * 4);
+        get(eblk, ix->eblk, ne * 2);
+        get(epos, ix->epos, (ne + 1) * 4);
+        get(seg, ix->seg, ne * 8 * 2);
+        get(lid, ix->lid, ne * 4);
+        get(wmeta, ix->wmeta, nl * WSEG * 8 * 2);
+        get(emax, ix->emax, ne);
+        get(wmax, ix->wmax, nl * WSEG);
     });
 }
 
@@ -2872,8 +2964,15 @@ int di_index_load_reference(const char *dir, uint32_t doc_lo, uint32_t doc_hi, i
                 }
             }
         });
-        int rc = di_index_create(term_off.data(), nt, pdoc.data(), pval.data(), doc_lo, doc_hi,
-                                 device, out);
+        // the parsed CSR goes to the device layout builder (its median time is below the
+        // host route's fastest at 100 k, 1.1 M and 8.8 M docs);
+        // DI_INDEX_LAYOUT=host: build_index() on host threads, the same bytes
+        const char *lay = std::getenv("DI_INDEX_LAYOUT");
+        const int rc = !(lay && std::strcmp(lay, "host") == 0)
+                           ? di_index_create_device(term_off.data(), nt, pdoc.data(), pval.data(),
+                                                    doc_lo, doc_hi, device, nullptr, 0, out)
+                           : di_index_create(term_off.data(), nt, pdoc.data(), pval.data(), doc_lo,
+                                             doc_hi, device, out);
         if (rc != DI_OK) throw Error{rc};
     });
 }

@@ -15,7 +15,9 @@ indexer.py:49-54 holds in a comment).
 inverted_index.dat) in DIR in the same process, from the encoder's device output: the bytes
 of `quantize` and `inverted_index` run over the impact TSV, without that file (--max_val:
 quantize's -m; --output_file_path is then optional and still writes the TSV).  One GPU:
-not with --pairwise, --doc_range or more than one rank.  DI_INDEX_TEXT_ROUTE=1 runs the
+not with --pairwise, --doc_range or more than one rank.  --index_layout host|device
+(DI_INDEX_LAYOUT overrides) says where the index object's blocked layout is built; the files
+do not depend on it.  DI_INDEX_TEXT_ROUTE=1 runs the
 three text steps into DIR instead (A/B).  The device route itself takes the pairwise model
 -- run(..., pairwise=True, inverted_index_path=DIR) and Indexer.build_index build the
 't1|t2' postings on the GPU -- but the command line still refuses the combination; that
@@ -50,11 +52,13 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
         num_processes=8, process_batch_size=50 * BATCH_SIZE, model_batch_size=BATCH_SIZE,
         tokenizer_path=None, max_length=None, precision="bf16x3", device=0, variant="xlmr",
         doc_range=None, pairwise=False, first_shard=True, inverted_index_path=None,
-        max_val=None):
+        max_val=None, index_layout="device"):
     """inverted_index_path: build the quantized index there on the device
     (Indexer.build_index's route) instead of / beside the impact TSV; output_file_path may
     then be None.  With pairwise=True the pair scores stay on the device too and the index
-    holds the 't1|t2' terms (IndexBuilder.append_pairwise)."""
+    holds the 't1|t2' terms (IndexBuilder.append_pairwise).  index_layout: "host" or
+    "device", where the index object's blocked layout is built (the files do not depend on
+    it)."""
     # --pairwise: DeepPairwiseImpact through the same Indexer (its lines add the
     # 't1|t2' entries and are sorted by score, pairwise_impact.py:98-129)
     model_cls = DeepPairwiseImpact if pairwise else DeepImpact
@@ -78,7 +82,7 @@ def run(collection_path, collection_type, output_file_path, model_checkpoint_pat
             n = _index_file(build, collection_path, collection_type,
                             output_file_path if output_file_path is not None else os.devnull,
                             process_batch_size, doc_range, start, first_shard)
-            build.inverted_index(max_val, inverted_index_path)
+            build.inverted_index(max_val, inverted_index_path, layout=index_layout)
             logger.info(f"Built the inverted index of {n} passages in {inverted_index_path} "
                         f"(max value {build.max_used})")
             return n
@@ -194,6 +198,9 @@ def main(argv=None):
                         "output, without the intermediate files; one GPU")
     p.add_argument("--max_val", type=float, default=None,
                    help="with --inverted_index_path: quantize's -m (default: the maximum)")
+    p.add_argument("--index_layout", choices=["host", "device"], default="device",
+                   help="with --inverted_index_path: where the index object's blocked device "
+                        "layout is built (DI_INDEX_LAYOUT overrides; the files are the same)")
     p.add_argument("--model_checkpoint_path", type=str, required=True)
     p.add_argument("--num_processes", type=int, default=8)
     p.add_argument("--process_batch_size", type=int, default=50 * BATCH_SIZE)
@@ -222,6 +229,8 @@ def main(argv=None):
         _check_index_route(p, a)
         if os.environ.get("DI_INDEX_TEXT_ROUTE") == "1":
             return _text_route(a)
+        if os.environ.get("DI_INDEX_LAYOUT") in ("host", "device"):
+            a.index_layout = os.environ["DI_INDEX_LAYOUT"]
     if a.doc_range is None and a.device is None:
         n = parallel.ranks_to_spawn(a.gpus)
         if n > 1:
@@ -242,7 +251,8 @@ def main(argv=None):
     run(a.collection_path, a.collection_type, out, a.model_checkpoint_path,
         a.num_processes, a.process_batch_size, a.model_batch_size, a.tokenizer_path,
         a.max_length, a.precision, device, a.variant, dr, a.pairwise, first_shard=rank == 0,
-        inverted_index_path=a.inverted_index_path, max_val=a.max_val)
+        inverted_index_path=a.inverted_index_path, max_val=a.max_val,
+        index_layout=a.index_layout)
     if world > 1:
         dist.barrier()
         if rank == 0:

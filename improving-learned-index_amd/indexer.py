@@ -294,7 +294,8 @@ class Indexer:
         """indexer.py:31-68: file.write('\\n'.join(lines) + '\\n')."""
         self.finish(self.submit(batch), file)
 
-    def build_index(self, documents_or_batches, max_val=None, index_path=None, file=None):
+    def build_index(self, documents_or_batches, max_val=None, index_path=None, file=None,
+                    layout="device"):
         """Index these documents and search them, in one process: the InvertedIndex the text
         route (index -> quantize -> inverted_index -> InvertedIndex(path)) gives for the
         same collection, without its files.  The round3 impacts of every device step stay
@@ -304,7 +305,9 @@ class Indexer:
         gives the index of index --pairwise -> quantize -> inverted_index, 't1|t2' terms
         included.  max_val: quantize's -m.
         index_path: also write vocab.txt / inverted_index.idx / inverted_index.dat there.
-        file: also write the impact TSV there, from the same encode."""
+        file: also write the impact TSV there, from the same encode.
+        layout: "host" or "device", where the scorer's blocked layout is built
+        (InvertedIndex.from_builder); the index is the same."""
         docs = documents_or_batches
         batches = [docs] if isinstance(docs, (list, tuple)) and (not docs or isinstance(docs[0], str)) \
             else docs
@@ -317,7 +320,7 @@ class Indexer:
             pending = handle
         if pending is not None:
             build.finish(pending, file)
-        ix = build.inverted_index(max_val, index_path)
+        ix = build.inverted_index(max_val, index_path, layout=layout)
         self.build_ms, self.last_build = build.ms, build
         return ix
 
@@ -494,7 +497,7 @@ class IndexBuild:
     def drain(self) -> None:
         pass
 
-    def inverted_index(self, max_val=None, index_path=None):
+    def inverted_index(self, max_val=None, index_path=None, layout="device"):
         """Quantize, number the terms, fetch the postings (sorted on the GPU) and create the
         device index -> InvertedIndex."""
         import time
@@ -508,7 +511,7 @@ class IndexBuild:
         t0 = time.perf_counter()
         self.max_used, _, _ = self.builder.quantize(len(self.table), max_val, timing=True)
         ix = InvertedIndex.from_builder(self.builder, self.table, device=self.device,
-                                        index_path=index_path, timing=True)
+                                        index_path=index_path, timing=True, layout=layout)
         self.ms["build"] += (time.perf_counter() - t0) * 1e3
         return ix
 

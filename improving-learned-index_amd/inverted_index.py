@@ -50,14 +50,21 @@ class InvertedIndex:
 
     @classmethod
     def from_builder(cls, builder: "_lib.IndexBuilder", table: "_lib.TermTable", device=None,
-                     doc_lo: int = 0, doc_hi: int = 0, index_path=None, timing=False):
+                     doc_lo: int = 0, doc_hi: int = 0, index_path=None, timing=False,
+                     layout: str = "device"):
         """The index of a quantized IndexBuilder, without the files in between: the same
         object as InvertedIndex(path) over the files the text route writes for the same
         collection.  The builder's postings come back in file order (sorted on the GPU) and
         go through di_index_create; ``vocab`` is the table's terms that kept a posting, in
         sorted() order -- with the 't1|t2' terms of a builder filled by append_pairwise
         among them.  index_path: also write vocab.txt / inverted_index.idx /
-        inverted_index.dat there."""
+        inverted_index.dat there.  layout="device" (the default: the faster route at every
+        measured size): the postings stay on the GPU and di_index_create_device
+        builds the blocked layout there; they visit the host only when index_path asks for the
+        files, copied once for the writer.  layout="host": the postings come to the host and
+        di_index_create builds the layout on host threads -- the same bytes."""
+        if layout not in ("host", "device"):
+            raise ValueError(f"layout must be 'host' or 'device', not {layout!r}")
         if getattr(builder, "term_count", None) is None:
             raise ValueError("IndexBuilder.quantize comes first")
         first_id, second_id, _ = builder.pair_terms()
@@ -65,7 +72,13 @@ class InvertedIndex:
             term_row, n_rows = table.rows_pairwise(builder.term_count, first_id, second_id)
         else:
             term_row, n_rows = table.rows(builder.term_count)
-        term_off, pdoc, pval = builder.postings(term_row, n_rows, timing=timing)
+        on_device = layout == "device"
+        term_off, pdoc, pval = builder.postings(term_row, n_rows, timing=timing, device=on_device)
+        d_post = (term_off, pdoc, pval)
+        if on_device and index_path is not None:
+            term_off = term_off.cpu().numpy()
+            pdoc = pdoc.cpu().numpy().view(np.uint32)
+            pval = pval.cpu().numpy()
         if index_path is not None and first_id.size:
             _lib.write_reference_index_pairwise(index_path, table, first_id, second_id, term_row,
                                                 n_rows, term_off, pdoc, pval)
@@ -77,7 +90,12 @@ class InvertedIndex:
                       else table.vocab(term_row))
         self.device = builder.device if device is None else device
         self.doc_lo, self.doc_hi = doc_lo, doc_hi
-        self._dev = DeviceIndex.from_postings(term_off, pdoc, pval, doc_lo, doc_hi, self.device)
+        if on_device:
+            self._dev = DeviceIndex.from_postings(*d_post, doc_lo, doc_hi, self.device,
+                                                  layout="device", timing=timing)
+        else:
+            self._dev = DeviceIndex.from_postings(term_off, pdoc, pval, doc_lo, doc_hi,
+                                                  self.device)
         self.set_min_impact(1)
         self.set_block_max(0.0)
         self.packed, self.packed_bytes = False, 0

@@ -84,6 +84,35 @@ int di_index_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pd
                     const uint8_t *pval, uint32_t doc_lo, uint32_t doc_hi, int device,
                     di_index **out);
 
+/* di_index_create with the blocked device layout built on the GPU: the same index, byte
+ * for byte (di_index_export), from the same arguments.  With DI_F_DEVICE_PTRS term_off,
+ * pdoc and pval are device pointers (e.g. di_index_builder_postings' device output) and only
+ * status words and sizes are read back; host pointers are copied to the device first.
+ * term_off is checked on the device (DI_EINVAL through an error word read once); the other
+ * errors are di_index_create's.  One deviation: a group of more than 2048 postings -- a doc
+ * repeated inside a term so that one 2048-doc wave segment of a block overfills, or
+ * DI_WLONG_MIN above 2049 with such a short sublist -- is DI_EINVAL here, where
+ * di_index_create takes it silently.  Runs on hip_stream and waits for it; its scratch (two
+ * 16-byte records per kept posting) is freed at return.  DI_F_TIMING (read with
+ * di_index_timing): "il_check", "il_input", "il_count", "il_scan", "il_compact", "il_hist",
+ * "il_scatter", "il_heads", "il_entries", "il_long", "il_segment", "il_deal". */
+int di_index_create_device(const int64_t *term_off, int64_t n_terms, const uint32_t *pdoc,
+                           const uint8_t *pval, uint32_t doc_lo, uint32_t doc_hi, int device,
+                           void *hip_stream, uint32_t flags, di_index **out);
+
+/* The device layout read back, of an index from either route (the counterpart of
+ * di_sparse_export).  di_index_layout: the (term, block) entries, the long sublists, the docs
+ * per block and whether the flat posting array exists; with di_index_info's n_terms and
+ * n_postings they size di_index_export's host arrays: post and post_flat [n_postings]
+ * (post_flat only when *has_flat), tb_start [n_terms + 1], eblk [n_ent], epos [n_ent + 1],
+ * seg [8 n_ent], lid [n_ent], wmeta [128 n_long], emax [n_ent], wmax [16 n_long].  Any
+ * pointer may be NULL. */
+int di_index_layout(const di_index *ix, int64_t *n_ent, int64_t *n_long, int32_t *block_docs,
+                    int32_t *has_flat);
+int di_index_export(const di_index *ix, uint32_t *post, uint32_t *post_flat, uint32_t *tb_start,
+                    uint16_t *eblk, uint32_t *epos, uint16_t *seg, uint32_t *lid, uint16_t *wmeta,
+                    uint8_t *emax, uint8_t *wmax);
+
 /* Native host builder of the reference files: replaces InvertedIndexCreator.run
  * (create.py:53-55) reading the collection like DeepImpactCollection
  * (src/deep_impact/indexing/deep_impact_collection.py:6-33).  Writes
@@ -92,7 +121,9 @@ int di_index_create(const int64_t *term_off, int64_t n_terms, const uint32_t *pd
 int di_build_reference_index(const char *collection_path, const char *out_dir);
 
 /* Reads <dir>/inverted_index.idx and <dir>/inverted_index.dat (create.py:45-51,
- * formats src/utils/defaults.py:22-37).  vocab.txt stays on the host side. */
+ * formats src/utils/defaults.py:22-37).  vocab.txt stays on the host side.  The files are
+ * parsed on host threads; the parsed CSR goes to di_index_create_device, or, with
+ * DI_INDEX_LAYOUT=host in the environment, to di_index_create (the same index). */
 int di_index_load_reference(const char *dir, uint32_t doc_lo, uint32_t doc_hi, int device,
                             di_index **out);
 
