@@ -18,11 +18,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 #include "di_common.h"
 #include "enc_common.h"
+#include "enc_handle.h"
 
 namespace di {
 
@@ -305,12 +308,21 @@ constexpr int ax_lds(int nw, int qtn, int kc = AX_KC) { return 4 * kc * 256 + nw
 // 384 tokens in one pass -- a wave's third tile runs the generic loop, the pair PIPE).
 // KC: keys per staged chunk (64; 32 halves the K / V buffers: the 4-wave form of the pruned
 // last layer, two workgroups per CU).
+#ifdef DI_ATTN_STAMP
+// Diagnostic build only (never the product's): every workgroup's first and last clock
+// reading (100 MHz) of one launch, in a buffer of their own that no kernel reads;
+// ax_launch prints the spread of the finish times (DI_ATTN_STAMP_FROM / _COUNT: which
+// launches of the process)
+__device__ unsigned long long ax_stamp[2][1024];
+#endif
+
 template <bool BAL, bool LAZY, bool PIPE = false, int NW = AX_WAVES, int QTN = AX_QT,
           int KC = AX_KC>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2)))
 attention_x3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu_seqlens, int H,
                     int n_heads, int n_pairs, bf16 *__restrict__ ctx_split,
                     const int32_t *__restrict__ qsel, const int32_t *__restrict__ cu_qsel,
+                    const int32_t *__restrict__ q_order, const int32_t *__restrict__ q_range,
                     int abl) {
     // abl (developer timing ablations, wrong results): 1 no softmax arithmetic, 2 no S^T
     // products, 4 no O^T products, 16 no second pass (documents past 256 queries)
@@ -322,6 +334,11 @@ attention_x3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, c = lane & 15;
+#ifdef DI_ATTN_STAMP
+    if (lane == 0)
+        atomicMin(&ax_stamp[0][blockIdx.x], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
     const int64_t ld = 6 * (int64_t)H;  // split row: 3H logical columns
     const uint32_t lds_base =
         (uint32_t)(uintptr_t)((__attribute__((address_space(3))) unsigned char *)lds);
@@ -330,21 +347,35 @@ attention_x3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
     static_assert(QTN == 2 || QTN == 3, "two or three query tiles per wave");
     constexpr int IMG = KC * 256, KVL = 4 * IMG;  // one K or V image; the four of them
 
-    // Work units: (pair, pass), pairs blockIdx.x, + gridDim.x, ... (persistent); the
-    // next unit's Q and first K / V chunk load while the current unit's last chunk
-    // computes.
+    // Work units: (pair, pass) (persistent); the next unit's Q and first K / V chunk load
+    // while the current unit's last chunk computes.  In round r this workgroup takes pair
+    // r * gridDim.x + blockIdx.x.  With a unit order (q_order: the documents longest first;
+    // q_range: the [lo, hi) of that list this launch computes) the pairs are counted along
+    // the list and odd rounds deal backwards, blockIdx.x gridDim.x - 1 first: a round's
+    // pairs cost nearly the same and what differences there are cancel from round to round,
+    // so every workgroup ends at nearly the same time, whatever the documents' lengths.
+    // Every quantity here is the same in all of a workgroup's waves (the barriers of the
+    // chunk loop depend on them).
     struct Unit {
-        int pair, pass, tok0, n, h, q0, nq;  // q0: ctx row of query 0; nq: queries
+        int r, pass, tok0, n, h, q0, nq;  // q0: ctx row of query 0; nq: queries
     };
-    auto make_unit = [&](int pr, int pass, Unit &u) {
-        const int doc = pr / n_heads;
-        u.pair = pr;
-        u.pass = pass;
-        u.h = pr % n_heads;
+    const int q_lo = q_order ? q_range[0] : 0;
+    const int n_units = q_order ? (q_range[1] - q_lo) * n_heads : n_pairs;
+    // round r's unit (pass 0), or false past the last pair
+    auto make_unit = [&](int r, Unit &u) {
+        const int gs = (int)gridDim.x, bx = (int)blockIdx.x;
+        const int64_t i = (int64_t)r * gs + ((q_order && (r & 1)) ? gs - 1 - bx : bx);
+        if (i >= n_units) return false;
+        const int di = (int)i / n_heads;
+        const int doc = q_order ? q_order[q_lo + di] : di;
+        u.r = r;
+        u.pass = 0;
+        u.h = (int)i - di * n_heads;
         u.tok0 = cu_seqlens[doc];
         u.n = cu_seqlens[doc + 1] - u.tok0;
         u.q0 = qsel ? cu_qsel[doc] : u.tok0;
         u.nq = qsel ? cu_qsel[doc + 1] - u.q0 : u.n;
+        return true;
     };
     // the unit after `u` with at least one token and one query, or false
     auto next_unit = [&](const Unit &u, Unit &nu) {
@@ -353,10 +384,8 @@ attention_x3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
             nu.pass = u.pass + 1;
             return true;
         }
-        for (int pr = u.pair + (int)gridDim.x; pr < n_pairs; pr += (int)gridDim.x) {
-            make_unit(pr, 0, nu);
+        for (int r = u.r + 1; make_unit(r, nu); ++r)
             if (nu.n > 0 && nu.nq > 0) return true;
-        }
         return false;
     };
     // chunk ci of unit u -> stage buffer b: key rows RPW wave..+RPW-1 of K and of V
@@ -426,13 +455,9 @@ attention_x3_kernel(const bf16 *__restrict__ qkv, const int32_t *__restrict__ cu
         }
 
     Unit cu;
-    {
-        int pr = blockIdx.x;
-        for (; pr < n_pairs; pr += (int)gridDim.x) {
-            make_unit(pr, 0, cu);
-            if (cu.n > 0 && cu.nq > 0) break;
-        }
-        if (pr >= n_pairs) return;
+    for (int r = 0;; ++r) {
+        if (!make_unit(r, cu)) return;  // (no unit, or none with a token and a query)
+        if (cu.n > 0 && cu.nq > 0) break;
     }
     bf16x8 qh[QTN][2], ql[QTN][2];
     const uint32_t qa = lds_base + KVL + wave * (QTN * AX_QTB) + lane * 16;
@@ -939,14 +964,177 @@ __builtin_amdgcn_sched_barrier(0);
         if (!more) break;
         cu = nu;
     }
+#ifdef DI_ATTN_STAMP
+    if (lane == 0)
+        atomicMax(&ax_stamp[1][blockIdx.x], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+#endif
 #undef AX_READ_K
 #undef AX_READ_VW
 #undef AX_SEL
 }
 
+// The unit order of one encode call: order[0 .. n_docs) = the documents by token count,
+// longest first, ties to the lower document (a counting sort over the lengths 0 ..
+// max_len, lengths outside clamped: whatever cu_seqlens holds, order is a permutation);
+// ctl = {0, n_long, n_docs, 0, n_docs}, n_long = documents of more than long_len tokens.
+// One workgroup: a histogram, its running sum from the longest length down, then thread b
+// places the documents of length b in document order, reading the lengths from LDS tiles.
+constexpr int AQ_THREADS = 1024, AQ_TILE = 4096;
+__global__ void __launch_bounds__(AQ_THREADS)
+attn_order_kernel(const int32_t *__restrict__ cu_seqlens, int n_docs, int max_len, int long_len,
+                  int32_t *__restrict__ order, int32_t *__restrict__ ctl) {
+    extern __shared__ int32_t aq_lds[];  // start[max_len + 1] | tile[AQ_TILE]
+    int32_t *start = aq_lds, *tile = aq_lds + (max_len + 1);
+    const int tid = threadIdx.x;
+    auto len_of = [&](int d) {
+        return min(max(cu_seqlens[d + 1] - cu_seqlens[d], 0), max_len);
+    };
+    for (int b = tid; b <= max_len; b += AQ_THREADS) start[b] = 0;
+    __syncthreads();
+    for (int d = tid; d < n_docs; d += AQ_THREADS) atomicAdd(&start[len_of(d)], 1);
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0, n_long = 0;
+        for (int b = max_len; b >= 0; --b) {
+            const int cnt = start[b];
+            start[b] = acc;
+            acc += cnt;
+            if (b == long_len + 1) n_long = acc;
+        }
+        ctl[0] = 0;
+        ctl[1] = n_long;
+        ctl[2] = n_docs;
+        ctl[3] = 0;
+        ctl[4] = n_docs;
+    }
+    __syncthreads();
+    for (int t0 = 0; t0 < n_docs; t0 += AQ_TILE) {
+        const int nt = min(AQ_TILE, n_docs - t0);
+        for (int i = tid; i < nt; i += AQ_THREADS) tile[i] = len_of(t0 + i);
+        __syncthreads();
+        for (int b = tid; b <= max_len; b += AQ_THREADS) {
+            int pos = start[b];  // (< n_docs: the histogram counted every document once)
+            for (int i = 0; i < nt; ++i)
+                if (tile[i] == b) order[pos++] = t0 + i;
+            start[b] = pos;
+        }
+        __syncthreads();
+    }
+}
+
+bool attn_order_ok(int max_positions) {
+    return max_positions >= 0 && (size_t)(max_positions + 1 + AQ_TILE) * 4 <= 64 * 1024;
+}
+
+void launch_attn_order(const int32_t *cu_seqlens, int n_docs, int max_positions, int32_t *order,
+                       int32_t *ctl, hipStream_t s) {
+    DI_REQUIRE(attn_order_ok(max_positions), DI_ERANGE, "attention order: max_positions %d",
+               max_positions);
+    hipLaunchKernelGGL(attn_order_kernel, dim3(1), dim3(AQ_THREADS),
+                       (size_t)(max_positions + 1 + AQ_TILE) * 4, s, cu_seqlens, n_docs,
+                       max_positions, AQ_LONG_LEN, order, ctl);
+    check_launch("attn_order");
+}
+
+int attn_queue_mode() {
+    static const int mode = [] {
+        const char *e = getenv("DI_ATTN_X3_QUEUE");
+        return e ? atoi(e) : 2;
+    }();
+    return mode;
+}
+
+namespace {
+
+// LDS of one CU and the most one workgroup may take (current device)
+void ax_lds_limits(int &per_cu, int &per_wg) {
+    int dev = 0, cu = 0, wg = 0;
+    DI_HIP(hipGetDevice(&dev));
+    DI_HIP(hipDeviceGetAttribute(&wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev);
+    per_wg = wg;
+    per_cu = std::max(cu, wg);
+}
+
+struct AxArgs {
+    const bf16 *qkv;
+    const int32_t *cu_seqlens;
+    int H, n_heads;
+    int64_t n_pairs;
+    bf16 *ctx_split;
+    const int32_t *qsel, *cu_qsel, *q_order, *q_range;
+    int abl;
+    hipStream_t s;
+};
+
+template <bool BL, bool LZ, bool PP, int NW, int QN, int KC>
+void ax_launch(const AxArgs &a) {
+    constexpr int LDS = ax_lds(NW, QN, KC);
+    const auto kern = attention_x3_kernel<BL, LZ, PP, NW, QN, KC>;
+    int dev = 0, per_cu = 0, per_wg = 0;
+    DI_HIP(hipGetDevice(&dev));
+    ax_lds_limits(per_cu, per_wg);
+    DI_REQUIRE(LDS <= per_wg, DI_ERANGE, "attention_x3: %d bytes of LDS, the device gives %d",
+               LDS, per_wg);
+    // the dynamic LDS limit: once per instantiation and device, not per launch
+    static std::atomic<uint64_t> set_on{0};
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (!(set_on.load(std::memory_order_acquire) & bit)) {
+        DI_HIP(hipFuncSetAttribute((const void *)kern,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        set_on.fetch_or(bit, std::memory_order_release);
+    }
+    const int grid = (int)std::min<int64_t>(a.n_pairs, (int64_t)n_cu() * (per_cu / LDS));
+#ifdef DI_ATTN_STAMP
+    unsigned long long *st = nullptr;
+    DI_HIP(hipGetSymbolAddress((void **)&st, HIP_SYMBOL(ax_stamp)));
+    DI_HIP(hipMemsetAsync(st, 0xFF, 1024 * 8, a.s));
+    DI_HIP(hipMemsetAsync(st + 1024, 0, 1024 * 8, a.s));
+#endif
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), LDS, a.s, a.qkv, a.cu_seqlens, a.H,
+                       a.n_heads, (int)a.n_pairs, a.ctx_split, a.qsel, a.cu_qsel, a.q_order,
+                       a.q_range, a.abl);
+    check_launch("attention_x3");
+#ifdef DI_ATTN_STAMP
+    static int n_launch = 0;
+    static const int from = getenv("DI_ATTN_STAMP_FROM") ? atoi(getenv("DI_ATTN_STAMP_FROM")) : 0;
+    static const int cnt = getenv("DI_ATTN_STAMP_COUNT") ? atoi(getenv("DI_ATTN_STAMP_COUNT")) : 0;
+    if (n_launch >= from && n_launch < from + cnt && grid <= 1024) {
+        static unsigned long long h[2][1024];
+        DI_HIP(hipStreamSynchronize(a.s));
+        DI_HIP(hipMemcpy(h, st, sizeof h, hipMemcpyDeviceToHost));
+        unsigned long long t0 = ~0ull, t1 = 0;
+        double sum = 0;
+        int nb = 0;
+        std::vector<unsigned long long> ends;
+        for (int i = 0; i < grid; ++i)
+            if (h[1][i]) {
+                t0 = std::min(t0, h[0][i]);
+                t1 = std::max(t1, h[1][i]);
+                ends.push_back(h[1][i]);
+                ++nb;
+            }
+        if (nb) {
+            std::sort(ends.begin(), ends.end());
+            for (auto e : ends) sum += (double)(e - t0);
+            const double span = (double)(t1 - t0), mean = sum / nb;
+            fprintf(stderr,
+                    "ax_stamp launch %d NW=%d qsel=%d list=%d grid=%d busy=%d span_us=%.1f "
+                    "mean_end=%.4f first_end=%.4f median_end=%.4f p90_end=%.4f tail=%.4f\n",
+                    n_launch, NW, a.qsel != nullptr, a.q_order != nullptr, grid, nb, span * 0.01,
+                    mean / span, (ends.front() - t0) / span, (ends[nb / 2] - t0) / span,
+                    (ends[nb * 9 / 10] - t0) / span, 1.0 - mean / span);
+        }
+    }
+    ++n_launch;
+#endif
+}
+
+}  // namespace
+
 void launch_attention_x3(const bf16 *qkv, const int32_t *cu_seqlens, int n_docs, int H,
                          bf16 *ctx_split, hipStream_t s, const int32_t *qsel,
-                         const int32_t *cu_qsel) {
+                         const int32_t *cu_qsel, const AttnQueue *q) {
     DI_REQUIRE(H % ATT_D == 0, DI_EINVAL, "hidden %d is not a multiple of the head dim 64", H);
     if (n_docs == 0) return;
     const int n_heads = H / ATT_D;
@@ -966,17 +1154,11 @@ void launch_attention_x3(const bf16 *qkv, const int32_t *cu_seqlens, int n_docs,
         const char *e = getenv("DI_ATTN_X3_ABLATE");
         return e ? atoi(e) : 0;
     }();
-#define AX_LAUNCH(BL, LZ, PP, NW, QN, KC)                                                      \
-    do {                                                                                       \
-        DI_HIP(hipFuncSetAttribute((const void *)attention_x3_kernel<BL, LZ, PP, NW, QN, KC>,  \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize,                 \
-                                   ax_lds(NW, QN, KC)));                                       \
-        hipLaunchKernelGGL((attention_x3_kernel<BL, LZ, PP, NW, QN, KC>),                      \
-                           dim3((int)std::min<int64_t>(                                        \
-                               n_pairs, (int64_t)n_cu() * (160 * 1024 / ax_lds(NW, QN, KC)))), \
-                           dim3(64 * NW), ax_lds(NW, QN, KC), s, qkv, cu_seqlens, H, n_heads,  \
-                           (int)n_pairs, ctx_split, qsel, cu_qsel, abl);                       \
-    } while (0)
+    // q (optional, launch_attn_order's list of this call): the launch walks a slice of the
+    // documents longest first (attention_x3_kernel); without it, the documents as they come
+    if (q && !q->order) q = nullptr;
+    AxArgs a{qkv, cu_seqlens, H, n_heads, n_pairs, ctx_split, qsel, cu_qsel,
+             q ? q->order : nullptr, q ? q->ctl + AQ_ALL : nullptr, abl, s};
     // The pruned last layer (qsel: the terms' rows, ~1/5 of the queries): 4-wave
     // workgroups with 32-key chunks, two per CU, so that a document's few query tiles
     // keep a workgroup's waves busy (DI_ATTN_X3_PRUNED=0: the full layers' kernel)
@@ -985,21 +1167,29 @@ void launch_attention_x3(const bf16 *qkv, const int32_t *cu_seqlens, int n_docs,
         return e ? atoi(e) : 1;
     }();
     if (qsel && pruned_variant == 1 && variant == 92) {
-        AX_LAUNCH(true, true, true, 4, 3, 32);
-        check_launch("attention_x3");
+        ax_launch<true, true, true, 4, 3, 32>(a);
+        return;
+    }
+    // Full layers with a list, two forms: the documents past one 192-query pass of the
+    // 4-wave form in the 8-wave kernel, the others in the 4-wave form (two workgroups per
+    // CU: a SIMD that one of them leaves idle runs the other's wave); each launch reads its
+    // slice from ctl and a workgroup without a unit ends at once
+    if (q && q->two_forms && !qsel && variant == 92) {
+        a.q_range = q->ctl + AQ_LONG;
+        ax_launch<true, true, true, AX_WAVES, 3, AX_KC>(a);
+        a.q_range = q->ctl + AQ_SHORT;
+        ax_launch<true, true, true, 4, 3, 32>(a);
         return;
     }
     // (r03 ab_attn, attention ms per step: BAL alone -3.5%, LAZY alone -5.6%, both -8.5%)
     switch (variant) {
-    case 12: AX_LAUNCH(true, true, false, AX_WAVES, AX_QT, AX_KC); break;
-    case 28: AX_LAUNCH(true, true, true, AX_WAVES, AX_QT, AX_KC); break;
-    case 60: AX_LAUNCH(true, true, true, 4, AX_QT, AX_KC); break;  // (with the Q regions: one per CU)
-    case 92: AX_LAUNCH(true, true, true, AX_WAVES, 3, AX_KC); break;  // three query tiles per wave
-    case 220: AX_LAUNCH(true, true, true, 4, 3, 32); break;  // + 4 waves, 32-key chunks
-    default: AX_LAUNCH(false, false, false, AX_WAVES, AX_QT, AX_KC); break;
+    case 12: ax_launch<true, true, false, AX_WAVES, AX_QT, AX_KC>(a); break;
+    case 28: ax_launch<true, true, true, AX_WAVES, AX_QT, AX_KC>(a); break;
+    case 60: ax_launch<true, true, true, 4, AX_QT, AX_KC>(a); break;  // (with the Q regions: one per CU)
+    case 92: ax_launch<true, true, true, AX_WAVES, 3, AX_KC>(a); break;  // three query tiles per wave
+    case 220: ax_launch<true, true, true, 4, 3, 32>(a); break;  // + 4 waves, 32-key chunks
+    default: ax_launch<false, false, false, AX_WAVES, AX_QT, AX_KC>(a); break;
     }
-#undef AX_LAUNCH
-    check_launch("attention_x3");
 }
 
 // One 32-key step of the online softmax for 16 queries (lane holds 8 raw scores of

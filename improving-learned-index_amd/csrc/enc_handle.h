@@ -23,6 +23,23 @@ struct PairRun {
     int max_len;
 };
 
+// The attention's unit order of one encode call (launch_attn_order): the documents sorted
+// by token count, longest first, and the slices of that list its launches walk.  ctl =
+// {0, n_long, n_docs, 0, n_docs}: documents [0, n_long) are longer than AQ_LONG_LEN tokens.
+// order == nullptr: no list, the launches walk the documents as they come.
+struct AttnQueue {
+    const int32_t *order = nullptr;  // [n_docs] (device)
+    const int32_t *ctl = nullptr;    // [AQ_CTL] (device)
+    bool two_forms = false;          // full layers: long and short documents in two launches
+};
+constexpr int AQ_CTL = 5, AQ_LONG = 0, AQ_SHORT = 1, AQ_ALL = 3;  // ctl index of a slice's [lo, hi)
+constexpr int AQ_LONG_LEN = 192;  // one pass of the 4-wave form
+// the knob DI_ATTN_X3_QUEUE (developer A/B): 0 no list, 1 one launch per layer, 2 two forms
+int attn_queue_mode();
+bool attn_order_ok(int max_positions);
+void launch_attn_order(const int32_t *cu_seqlens, int n_docs, int max_positions, int32_t *order,
+                       int32_t *ctl, hipStream_t s);
+
 }  // namespace di
 
 struct di_encoder {
@@ -59,6 +76,8 @@ struct di_encoder {
     // ordering's scratch
     di::DevBuf ent_single, ent_pair, ent_pos;
     di::PairOrderWs order;
+    di::DevBuf aq_order, aq_ctl;  // bf16x3: the attention's unit order of the call in flight
+    di::AttnQueue aq;
     di::DevBuf pinfo;  // di_encode_pairs: (n_tokens, max_len, error bits) of the pack
     di::Timer timer;
 };

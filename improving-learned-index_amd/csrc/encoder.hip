@@ -34,7 +34,7 @@ void launch_attention(const T *qk, const T *vt, const int32_t *cu_seqlens, int n
 void launch_gemm256(int epi, const GemmArgs &g, hipStream_t s);
 void launch_attention_x3(const bf16 *qkv, const int32_t *cu_seqlens, int n_docs, int H,
                          bf16 *ctx_split, hipStream_t s, const int32_t *qsel = nullptr,
-                         const int32_t *cu_qsel = nullptr);
+                         const int32_t *cu_qsel = nullptr, const AttnQueue *q = nullptr);
 void launch_scatter_term_rows(const bf16 *Xg, const int32_t *cu_seq, const int32_t *cu_terms,
                               const int32_t *term_tok, int n_docs, int W, int64_t ld, bf16 *X,
                               hipStream_t s);
@@ -277,6 +277,10 @@ void di::ensure_workspace(di_encoder *e, int64_t M, int n_docs, int64_t n_terms)
     e->cut.reserve((size_t)(n_docs + 1) * 4);
     e->tt.reserve((size_t)std::max<int64_t>(n_terms, 1) * 4);
     e->err.reserve(16);
+    if (e->split) {  // the attention's unit order (launch_attn_order)
+        e->aq_order.reserve((size_t)std::max(e->cap_docs, n_docs) * 4);
+        e->aq_ctl.reserve(AQ_CTL * 4);
+    }
     if (e->has_pair) {  // (Mx grows in di_encode_pairwise, by the batch's sum of T^2)
         e->uv.reserve((size_t)std::max<int64_t>(n_terms, 1) * 8);
         e->cu_sq.reserve((size_t)(n_docs + 1) * 8);
@@ -561,7 +565,7 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
             TimedLaunch tl(e->timer, timing, "attention", s);
             if (sp)
                 launch_attention_x3(e->qk.as<bf16>(), d_cu, n_docs, H, e->ctx.as<bf16>(), s,
-                                    prune ? d_tt : nullptr, prune ? d_ct : nullptr);
+                                    prune ? d_tt : nullptr, prune ? d_ct : nullptr, &e->aq);
             else
                 launch_attention_v3(e->qk.as<bf16>(), d_cu, n_docs, max_len, H,
                                     e->ctx.as<bf16>(), s, prune ? d_tt : nullptr,
@@ -701,7 +705,7 @@ void forward_split(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int
         {
             TimedLaunch tl(e->timer, timing, "attention", s);
             launch_attention_x3(e->qk.as<bf16>(), d_cu, n_docs, H, ctx, s,
-                                prune ? d_tt : nullptr, prune ? d_ct : nullptr);
+                                prune ? d_tt : nullptr, prune ? d_ct : nullptr, &e->aq);
         }
         if (prune) {  // the terms' residual rows, packed into Hff (free until FFN1)
             TimedLaunch tl(e->timer, timing, "gather_rows", s);
@@ -878,6 +882,17 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
         }
         run = PairRun{d_tt, d_cut, e->cu_sq.as<int64_t>(), max_len};
         if (n_pairs > 0) e->pair_run = &run;
+    }
+    // bf16x3: the attention's launches of this call walk the documents longest first
+    e->aq = AttnQueue{};
+    if (e->split && n_tokens > 0 && attn_queue_mode() > 0 &&
+        attn_order_ok(e->cfg.max_positions)) {
+        TimedLaunch tl(e->timer, timing, "attn_order", s);
+        launch_attn_order(d_cu, n_docs, e->cfg.max_positions, e->aq_order.as<int32_t>(),
+                          e->aq_ctl.as<int32_t>(), s);
+        e->aq.order = e->aq_order.as<int32_t>();
+        e->aq.ctl = e->aq_ctl.as<int32_t>();
+        e->aq.two_forms = attn_queue_mode() >= 2;
     }
     // pruned last layer (bf16 folded and bf16x3 paths, term output)
     const bool prune = !token_out && (e->split || (e->esz == 2 && e->folded)) &&
