@@ -162,14 +162,15 @@ struct GemmArgs {
     int64_t a_rows;       // rows of A that may be read (>= M; slack lets 256-row tiles
                           // read past M without clamping)
     int tune_gm;          // 256-tile kernel: M tiles per group in the tile order (0 = default)
-    int ablate;           // profiling only (tools/gemm_check): 1 = skip the epilogue
-    float ln_eps;
+    int ablate;           // profiling only (tools/gemm_check), bits the 256-tile kernel tests:
+                          // 2 = no GELU, 4 = no output stores (both: wrong results),
+                          // 8 = the erf GELU for bf16 outputs too (A/B of the two forms)
     // LayerNorm folding: row statistics as float4 partials (sum, sumsq, dot, 0) per
-    // 256-column tile: stats[t * stats_ld + row], t < n_part
+    // 256-column tile: stats[t * stats_ld + row], t < N / 256
     const float2 *row_ln;     // EPI_FOLD*: (rstd, -rstd mean) of A's rows; EPI_RESID_STATS:
                               // of resid's rows (null: plain residual)
     float4 *stats_out;        // EPI_RESID_STATS
-    int stats_ld, n_part, ln_h;
+    int stats_ld;
     const float *col_s, *col_c;          // EPI_FOLD*
     const float *res_gamma, *res_beta;   // EPI_RESID_STATS: LN params of resid
     const float *head_wg;                // EPI_RESID_STATS: w * gamma for the dot partial

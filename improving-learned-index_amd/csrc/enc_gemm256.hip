@@ -40,6 +40,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "di_common.h"
@@ -60,9 +61,91 @@ constexpr int G2_PAR_ROW = 0, G2_PAR_C0 = 2048, G2_PAR_C1 = 3072, G2_PAR_C2 = 40
               G2_PAR_C3 = 5120;
 constexpr int G2_LDS = 2 * G2_BUF + 2 * G2_PARSZ;
 
-// Epilogue row store (16 B per lane).
-__device__ __forceinline__ void g2_store(bf16 *p, const bf16x8 &v) {
-    *reinterpret_cast<bf16x8 *>(p) = v;
+// ---- epilogue toolkit: what the epilogues do with a lane's chunk (8 consecutive columns
+// of one row), each written once ------------------------------------------------------
+// Row formats of the output (and the residual): bf16 rows; split rows (every 32 columns as
+// 32 hi then 32 lo bf16, see split_col); f32 rows (the fp32-faithful pre-LayerNorm sums).
+enum G2Fmt { G2_BF16, G2_SPLIT, G2_F32 };
+template <int EPI, bool SPLIT>
+constexpr G2Fmt g2_out_fmt() {
+    return !SPLIT ? G2_BF16 : EPI == EPI_BIAS_RESID ? G2_F32 : G2_SPLIT;
+}
+
+// A wave's 128 x 64 block of a row-major buffer in format F, row stride ld elements: a
+// wave-uniform base (row row_w, column col_w) + mt * (16 rows) in SGPRs, and one 32-bit
+// lane offset (row lane&15, column (lane>>4)*8) -- no 64-bit pointer per row held across
+// the prefetch.  (chunk() takes the stride again: with a copy kept in the object the
+// compiler loads the kernel arguments before the first prologue and five instantiations
+// take 2 to 8 more VGPRs.)
+template <G2Fmt F>
+struct G2Rows {
+    static constexpr int ESZ = F == G2_F32 ? 4 : 2;
+    static constexpr int HS = F == G2_BF16 ? 64 : 128;  // bytes per 32 columns
+    char *base;
+    uint32_t lane_off;
+    __device__ __forceinline__ G2Rows(const void *buf, int ld, int64_t row_w, int64_t col_w,
+                                      int lane)
+        : base(static_cast<char *>(const_cast<void *>(buf)) +
+               (row_w * ld + (F == G2_SPLIT ? 2 * col_w : col_w)) * ESZ),
+          lane_off((uint32_t)(((lane & 15) * ld + (lane >> 4) * 8) * ESZ)) {}
+    // the lane's chunk of A fragment mt, column half h
+    __device__ __forceinline__ char *chunk(int mt, int h, int ld) const {
+        return base + (int64_t)mt * 16 * ld * ESZ + h * HS + lane_off;
+    }
+};
+
+// Residual read: the chunk's 8 values from a bf16 row, or hi + lo from a split row (the lo
+// chunk 64 bytes on).
+template <bool SPLIT>
+__device__ __forceinline__ void g2_resid8(const char *rp, float (&r)[8]) {
+    const bf16x8 rh = *reinterpret_cast<const bf16x8 *>(rp);
+    if constexpr (SPLIT) {
+        const bf16x8 rl = *reinterpret_cast<const bf16x8 *>(rp + 64);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = (float)rh[e] + (float)rl[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) r[e] = (float)rh[e];
+    }
+}
+
+// Round-and-store of a bf16 / split chunk, in two steps (EPI_RESID_STATS takes its
+// statistics from the rounded values in between): hi = bf16(v), split rows also
+// lo = bf16(v - hi); 16 B per lane and store, the lo chunk 64 bytes on.
+template <bool SPLIT>
+__device__ __forceinline__ void g2_round8(const float (&v)[8], bf16x8 &hi, bf16x8 &lo) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        hi[e] = split_hi(v[e]);
+        if constexpr (SPLIT) lo[e] = split_lo(v[e]);
+    }
+}
+template <bool SPLIT>
+__device__ __forceinline__ void g2_store8(char *op, const bf16x8 &hi, const bf16x8 &lo) {
+    *reinterpret_cast<bf16x8 *>(op) = hi;
+    if constexpr (SPLIT) *reinterpret_cast<bf16x8 *>(op + 64) = lo;
+}
+template <G2Fmt F>
+__device__ __forceinline__ void g2_round_store8(char *op, const float (&v)[8]) {
+    if constexpr (F == G2_F32) {
+        *reinterpret_cast<float4 *>(op) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4 *>(op + 16) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        bf16x8 hi, lo;
+        g2_round8<F == G2_SPLIT>(v, hi, lo);
+        g2_store8<F == G2_SPLIT>(op, hi, lo);
+    }
+}
+
+// GELU of the FFN1 epilogues: the erf form for split (fp32-faithful) outputs, the bf16
+// form otherwise.  ablate bit 2: none; bit 8: the erf form for bf16 outputs too (A/B).
+template <bool SPLIT>
+__device__ __forceinline__ void g2_gelu8(float (&v)[8], int ablate) {
+    if (ablate & 2) return;
+    if (SPLIT || (ablate & 8))
+        gelu_erf8(v);
+    else
+        gelu_bf16_8(v);
 }
 
 // Global stores one wave issues in the store phase of a full tile (every row < M):
@@ -368,13 +451,12 @@ __global__ void __launch_bounds__(G2_T) gemm256_kernel(GemmArgs g) {
         int m0e = m0;  // opaque: keeps the per-row epilogue offsets out of the K loop
         asm volatile("" : "+s"(m0e));
         const int row_l = m0e + wr * 128 + (lane & 15);
-        // global addresses: a wave-uniform base (row m0 + wr*128, column n0 + wc*64) +
-        // mt * (16 rows) in SGPRs, and one 32-bit lane offset (row lane&15, column
-        // (lane>>4)*8) -- no 64-bit pointer per row held across the prefetch
+        // the wave's block of the global rows (G2Rows): row m0 + wr*128, column n0 + wc*64
         const int64_t row_w = m0e + wr * 128, col_w = n0 + wc * 64;
-        auto lane_off = [&](int ld, int esz) {
-            return (uint32_t)(((lane & 15) * ld + (lane >> 4) * 8) * esz);
-        };
+        constexpr G2Fmt OUT = g2_out_fmt<EPI, SPLIT>();
+        constexpr G2Fmt RES = SPLIT ? G2_SPLIT : G2_BF16;  // the residual rows (ld 2N / N)
+        // accumulator element of (A fragment mt, column half h, column e of the chunk)
+#define G2_ACC(mt, h, e) acc[mt][2 * (h) + ((e) >> 2)][(e) & 3]
         const bool vtile = EPI == EPI_QKV && n0 >= 2 * g.hidden;
         const unsigned char *par = lds + G2_PAR + pb * G2_PARSZ;
         // tile-local indices into the staged parameters
@@ -420,32 +502,18 @@ __global__ void __launch_bounds__(G2_T) gemm256_kernel(GemmArgs g) {
                     asm volatile("" : "+v"(vc[mt]));  // ahead of the prefetch
             }
             if constexpr (EPI == EPI_BIAS_RESID) {  // acc <- (acc + bias) + resid
-                // (SPLIT: split residual rows, stride 2N, 32-column chunks of hi then lo).
                 const int rld = SPLIT ? 2 * N : N;
-                const char *rbase = static_cast<const char *>(g.resid) +
-                                    (row_w * rld + (SPLIT ? 2 * col_w : col_w)) * 2;
-                const uint32_t rlo = lane_off(rld, 2);
+                const G2Rows<RES> res(g.resid, rld, row_w, col_w, lane);
 #pragma unroll
                 for (int mt = 0; mt < 8; ++mt) {
                     if (!FULL && row_l + mt * 16 >= M) continue;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const char *rp = rbase + (int64_t)mt * 16 * rld * 2 + h * (SPLIT ? 128 : 64) + rlo;
                         float r[8];
-                        if constexpr (SPLIT) {
-                            const bf16x8 rh = *reinterpret_cast<const bf16x8 *>(rp);
-                            const bf16x8 rl = *reinterpret_cast<const bf16x8 *>(rp + 64);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) r[e] = (float)rh[e] + (float)rl[e];
-                        } else {
-                            const bf16x8 rv = *reinterpret_cast<const bf16x8 *>(rp);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) r[e] = (float)rv[e];
-                        }
+                        g2_resid8<SPLIT>(res.chunk(mt, h, rld), r);
 #pragma unroll
                         for (int e = 0; e < 8; ++e)
-                            acc[mt][2 * h + (e >> 2)][e & 3] =
-                                (acc[mt][2 * h + (e >> 2)][e & 3] + bias_v[h][e]) + r[e];
+                            G2_ACC(mt, h, e) = (G2_ACC(mt, h, e) + bias_v[h][e]) + r[e];
                     }
                 }
             }
@@ -490,53 +558,31 @@ __global__ void __launch_bounds__(G2_T) gemm256_kernel(GemmArgs g) {
                 // then 32 lo; the statistics are those of hi + lo, the value the
                 // consumer GEMMs read)
                 const int rld = SPLIT ? 2 * N : N;
-                constexpr int HS = SPLIT ? 128 : 64;  // bytes per 32 columns
-                const char *rbase = static_cast<const char *>(g.resid) +
-                                    (row_w * rld + (SPLIT ? 2 * col_w : col_w)) * 2;
-                const uint32_t rlo = lane_off(rld, 2);
-                char *ob = static_cast<char *>(g.out) +
-                           (row_w * g.ld_out + (SPLIT ? 2 * col_w : col_w)) * 2;
-                const uint32_t olo = lane_off(g.ld_out, 2);
+                const G2Rows<RES> res(g.resid, rld, row_w, col_w, lane);
+                const G2Rows<OUT> out(g.out, g.ld_out, row_w, col_w, lane);
 #pragma unroll
                 for (int mt = 0; mt < 8; ++mt) {
                     if (!FULL && row_l + mt * 16 >= M) continue;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const char *rp = rbase + (int64_t)mt * 16 * rld * 2 + h * HS + rlo;
-                        float r[8];
-                        if constexpr (SPLIT) {
-                            const bf16x8 rh = *reinterpret_cast<const bf16x8 *>(rp);
-                            const bf16x8 rl = *reinterpret_cast<const bf16x8 *>(rp + 64);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) r[e] = (float)rh[e] + (float)rl[e];
-                        } else {
-                            const bf16x8 rv = *reinterpret_cast<const bf16x8 *>(rp);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) r[e] = (float)rv[e];
-                        }
-                        bf16x8 o, ol;
+                        float r[8], y[8];
+                        g2_resid8<SPLIT>(res.chunk(mt, h, rld), r);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const float res = fmaf(gm[h][e], fmaf(rr[mt], r[e], rs[mt]), bt[h][e]);
-                            const float y = acc[mt][2 * h + (e >> 2)][e & 3] + bias_v[h][e] + res;
-                            float yb;
-                            if constexpr (SPLIT) {
-                                o[e] = split_hi(y);
-                                ol[e] = split_lo(y);
-                                yb = (float)o[e] + (float)ol[e];
-                            } else {
-                                o[e] = (bf16)y;
-                                yb = (float)o[e];
-                            }
+                            const float ln = fmaf(gm[h][e], fmaf(rr[mt], r[e], rs[mt]), bt[h][e]);
+                            y[e] = G2_ACC(mt, h, e) + bias_v[h][e] + ln;
+                        }
+                        bf16x8 o, ol;
+                        g2_round8<SPLIT>(y, o, ol);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            float yb = (float)o[e];  // the rounded out: the bf16, or hi + lo
+                            if constexpr (SPLIT) yb += (float)ol[e];
                             ss[mt] += yb;
                             sq[mt] = fmaf(yb, yb, sq[mt]);
                             sd[mt] = fmaf(yb, wg[h][e], sd[mt]);
                         }
-                        if (!(g.ablate & 4)) {
-                            char *op = ob + (int64_t)mt * 16 * g.ld_out * 2 + h * HS + olo;
-                            g2_store(reinterpret_cast<bf16 *>(op), o);
-                            if constexpr (SPLIT) g2_store(reinterpret_cast<bf16 *>(op + 64), ol);
-                        }
+                        if (!(g.ablate & 4)) g2_store8<SPLIT>(out.chunk(mt, h, g.ld_out), o, ol);
                     }
                 }
                 // partials: the 4 lane groups (lanes l, l^16, l^32, l^48 share a row),
@@ -603,96 +649,37 @@ __global__ void __launch_bounds__(G2_T) gemm256_kernel(GemmArgs g) {
                         for (int e = 0; e < 8; ++e)
                             *reinterpret_cast<bf16 *>(
                                 vb + (uint32_t)((((lane >> 4) * 8 + h * 32 + e) * g.ld_v + vc[mt]) * 2)) =
-                                (bf16)(acc[mt][2 * h + (e >> 2)][e & 3] + bias_v[h][e]);
-                }
-            } else if constexpr (FOLD) {
-                // LN folded into this GEMM: y = r acc - r mu s + c  (per row r, mu; per
-                // column s, c); row-major order: both 64-byte halves of a row's 128-byte
-                // segment are stored by consecutive instructions
-                // (SPLIT: A holds split rows of the un-normalised x, the output split rows)
-                constexpr int HS = SPLIT ? 128 : 64;  // bytes per 32 columns
-                char *ob = static_cast<char *>(g.out) +
-                           (row_w * g.ld_out + (SPLIT ? 2 * col_w : col_w)) * 2;
-                const uint32_t olo = lane_off(g.ld_out, 2);
-#pragma unroll
-                for (int mt = 0; mt < 8; ++mt) {
-                    const int row = row_l + mt * 16;
-                    if (!FULL && row >= M) continue;
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        float v[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            v[e] = fmaf(ra[mt], acc[mt][2 * h + (e >> 2)][e & 3],
-                                        fmaf(rb[mt], cs2[h][e], bias_v[h][e]));
-                        if constexpr (EPI == EPI_FOLD_GELU) {
-                            if (!(g.ablate & 2)) {
-                                if (SPLIT || (g.ablate & 8)) gelu_erf8(v);  // (A/B: the erf form)
-                                else gelu_bf16_8(v);
-                            }
-                        }
-                        if (g.ablate & 4) continue;
-                        char *op = ob + (int64_t)mt * 16 * g.ld_out * 2 + h * HS + olo;
-                        if constexpr (SPLIT) {
-                            bf16x8 hv, lv;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) hv[e] = split_hi(v[e]), lv[e] = split_lo(v[e]);
-                            g2_store(reinterpret_cast<bf16 *>(op), hv);
-                            g2_store(reinterpret_cast<bf16 *>(op + 64), lv);
-                        } else {
-                            bf16x8 o;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
-                            g2_store(reinterpret_cast<bf16 *>(op), o);
-                        }
-                    }
+                                (bf16)(G2_ACC(mt, h, e) + bias_v[h][e]);
                 }
             } else if constexpr (RS) {
                 // (stored with the statistics, before the prefetch)
             } else {
-                // element size and column of the output rows: bf16 rows; SPLIT: f32 rows
-                // (pre-LN) or split rows (ld_out = 2N: hi chunk then lo)
-                constexpr bool F32 = SPLIT && EPI == EPI_BIAS_RESID;
-                constexpr int ESZ = F32 ? 4 : 2;
-                constexpr int HSTEP = F32 ? 128 : (SPLIT ? 128 : 64);  // bytes per 32 columns
-                char *ob = static_cast<char *>(g.out) +
-                           (row_w * g.ld_out + ((SPLIT && !F32) ? 2 * col_w : col_w)) * ESZ;
-                const uint32_t olo = lane_off(g.ld_out, ESZ);
+                // row-major order: both halves of a row's segment are stored by consecutive
+                // instructions.  The value: LN folded into this GEMM, y = r acc - r mu s + c
+                // (per row r, mu; per column s, c; SPLIT: A holds split rows of the
+                // un-normalised x); acc + bias; or acc alone (EPI_BIAS_RESID: (1) added
+                // the bias and the residual)
+                const G2Rows<OUT> out(g.out, g.ld_out, row_w, col_w, lane);
 #pragma unroll
                 for (int mt = 0; mt < 8; ++mt) {
-                    const int row = row_l + mt * 16;
-                    if (!FULL && row >= M) continue;
+                    if (!FULL && row_l + mt * 16 >= M) continue;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         float v[8];
 #pragma unroll
-                        for (int e = 0; e < 8; ++e)
-                            v[e] = EPI == EPI_BIAS_RESID ? acc[mt][2 * h + (e >> 2)][e & 3]
-                                                         : acc[mt][2 * h + (e >> 2)][e & 3] +
-                                                               bias_v[h][e];
-                        if constexpr (EPI == EPI_BIAS_GELU) {
-                            if (!(g.ablate & 2)) {
-                                if (SPLIT || (g.ablate & 8)) gelu_erf8(v);
-                                else gelu_bf16_8(v);
-                            }
+                        for (int e = 0; e < 8; ++e) {
+                            if constexpr (FOLD)
+                                v[e] = fmaf(ra[mt], G2_ACC(mt, h, e),
+                                            fmaf(rb[mt], cs2[h][e], bias_v[h][e]));
+                            else if constexpr (EPI == EPI_BIAS_RESID)
+                                v[e] = G2_ACC(mt, h, e);
+                            else
+                                v[e] = G2_ACC(mt, h, e) + bias_v[h][e];
                         }
+                        if constexpr (EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_GELU)
+                            g2_gelu8<SPLIT>(v, g.ablate);
                         if (g.ablate & 4) continue;
-                        char *op = ob + (int64_t)mt * 16 * g.ld_out * ESZ + h * HSTEP + olo;
-                        if constexpr (F32) {
-                            *reinterpret_cast<float4 *>(op) = make_float4(v[0], v[1], v[2], v[3]);
-                            *reinterpret_cast<float4 *>(op + 16) = make_float4(v[4], v[5], v[6], v[7]);
-                        } else if constexpr (SPLIT) {  // 8 columns of one 32-column chunk
-                            bf16x8 hv, lv;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) hv[e] = split_hi(v[e]), lv[e] = split_lo(v[e]);
-                            g2_store(reinterpret_cast<bf16 *>(op), hv);
-                            g2_store(reinterpret_cast<bf16 *>(op + 64), lv);
-                        } else {
-                            bf16x8 o8;
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) o8[e] = (bf16)v[e];
-                            g2_store(reinterpret_cast<bf16 *>(op), o8);
-                        }
+                        g2_round_store8<OUT>(out.chunk(mt, h, g.ld_out), v);
                     }
                 }
             }
@@ -719,6 +706,7 @@ __global__ void __launch_bounds__(G2_T) gemm256_kernel(GemmArgs g) {
 #undef G2_READ_B
 #undef G2_MFMA
 #undef G2_SYNC_READS
+#undef G2_ACC
 }
 #undef G2_BAR
 #undef G2_WAITV
@@ -747,46 +735,36 @@ void launch_gemm256(int epi, const GemmArgs &g, hipStream_t s) {
     // otherwise queue behind the next tile's prefetch: measured O 0.31 -> 0.36 ms)
     const bool resid = epi == EPI_BIAS_RESID || epi == EPI_RESID_STATS;
     const dim3 grid(resid ? n_tiles : std::min(n_tiles, n_cu()));
-    if (g.split) {
-        switch (epi) {
-#define G2_SCASE(E)                                                                            \
-    case E:                                                                                    \
-        DI_HIP(hipFuncSetAttribute((const void *)gemm256_kernel<E, true>,                      \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS));       \
-        hipLaunchKernelGGL((gemm256_kernel<E, true>), grid, dim3(G2_T), G2_LDS, s, g);         \
-        break;
-            G2_SCASE(EPI_BIAS)
-            G2_SCASE(EPI_BIAS_GELU)
-            G2_SCASE(EPI_BIAS_RESID)
-            G2_SCASE(EPI_FOLD)
-            G2_SCASE(EPI_FOLD_GELU)
-            G2_SCASE(EPI_RESID_STATS)
-#undef G2_SCASE
-            default:
-                fail(DI_EINVAL, "bad split GEMM epilogue");
-        }
-        check_launch("gemm256_split");
-        return;
+    // the instantiations by [split][GemmEpi value]; null: none (4 is no epilogue, the
+    // split QKV projection is EPI_BIAS)
+    typedef void (*Kernel)(GemmArgs);
+    static const Kernel kernels[2][8] = {
+        {gemm256_kernel<EPI_BIAS, false>, gemm256_kernel<EPI_BIAS_GELU, false>,
+         gemm256_kernel<EPI_BIAS_RESID, false>, gemm256_kernel<EPI_QKV, false>, nullptr,
+         gemm256_kernel<EPI_FOLD, false>, gemm256_kernel<EPI_FOLD_GELU, false>,
+         gemm256_kernel<EPI_RESID_STATS, false>},
+        {gemm256_kernel<EPI_BIAS, true>, gemm256_kernel<EPI_BIAS_GELU, true>,
+         gemm256_kernel<EPI_BIAS_RESID, true>, nullptr, nullptr,
+         gemm256_kernel<EPI_FOLD, true>, gemm256_kernel<EPI_FOLD_GELU, true>,
+         gemm256_kernel<EPI_RESID_STATS, true>}};
+    static_assert(EPI_BIAS == 0 && EPI_BIAS_GELU == 1 && EPI_BIAS_RESID == 2 && EPI_QKV == 3 &&
+                      EPI_FOLD == 5 && EPI_FOLD_GELU == 6 && EPI_RESID_STATS == 7,
+                  "kernels[] is indexed by the epilogue's value");
+    const int sp = g.split ? 1 : 0;
+    const Kernel kern = epi >= 0 && epi < 8 ? kernels[sp][epi] : nullptr;
+    DI_REQUIRE(kern, DI_EINVAL, "gemm256: bad%s GEMM epilogue %d", sp ? " split" : "", epi);
+    // the dynamic LDS limit: once per instantiation and device, not per launch
+    static std::atomic<uint64_t> set_on[2][8];
+    int dev = 0;
+    DI_HIP(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (!(set_on[sp][epi].load(std::memory_order_acquire) & bit)) {
+        DI_HIP(hipFuncSetAttribute((const void *)kern,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS));
+        set_on[sp][epi].fetch_or(bit, std::memory_order_release);
     }
-    switch (epi) {
-#define G2_CASE(E)                                                                             \
-    case E:                                                                                    \
-        DI_HIP(hipFuncSetAttribute((const void *)gemm256_kernel<E, false>,                     \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS));       \
-        hipLaunchKernelGGL((gemm256_kernel<E, false>), grid, dim3(G2_T), G2_LDS, s, g);        \
-        break;
-        G2_CASE(EPI_BIAS)
-        G2_CASE(EPI_BIAS_GELU)
-        G2_CASE(EPI_BIAS_RESID)
-        G2_CASE(EPI_QKV)
-        G2_CASE(EPI_FOLD)
-        G2_CASE(EPI_FOLD_GELU)
-        G2_CASE(EPI_RESID_STATS)
-#undef G2_CASE
-        default:
-            fail(DI_EINVAL, "bad GEMM epilogue");
-    }
-    check_launch("gemm256");
+    hipLaunchKernelGGL(kern, grid, dim3(G2_T), G2_LDS, s, g);
+    check_launch(sp ? "gemm256_split" : "gemm256");
 }
 
 }  // namespace di

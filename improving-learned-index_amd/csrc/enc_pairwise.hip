@@ -43,7 +43,7 @@ __host__ __device__ __forceinline__ size_t pa_lds_floats(int n, int T) {
 }
 
 // Operand loaders: 4 consecutive logical columns of a Q or K row as f32.
-struct LoadF32 {  // forward<float>: qk [M][2H], Q | K row-major
+struct LoadF32 {  // the fp32 forward: qk [M][2H], Q | K row-major
     const float *p;
     int H;
     __device__ __forceinline__ f32x4 q(int64_t row, int col) const {

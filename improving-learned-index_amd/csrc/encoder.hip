@@ -305,135 +305,21 @@ void pair_attn_layer(di_encoder *e, const int32_t *d_cu, int n_docs, bool timing
                      e->cfg.hidden, e->Mx.as<float>(), e->err.as<int32_t>(), s);
 }
 
-template <typename T>
-void forward(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_docs, int64_t M,
-             int max_len, bool timing, hipStream_t s) {
-    const auto &c = e->cfg;
-    const int H = c.hidden, F = c.intermediate;
-    const int pos_offset = (c.variant == DI_VARIANT_XLMR) ? c.pad_id + 1 : 0;
-    T *X = e->X.as<T>(), *X1 = e->X1.as<T>();
-    {
-        TimedLaunch tl(e->timer, timing, "embed_ln", s);
-        launch_embed_ln<T>(d_ids, d_cu, n_docs, (int)M, H, e->word.as<T>(), e->pos.as<T>(),
-                           e->type0.as<T>(), e->emb_g.as<float>(), e->emb_b.as<float>(),
-                           c.layer_norm_eps, pos_offset, c.vocab_size, c.max_positions, X,
-                           e->err.as<int32_t>(), s);
-    }
-    // attention path: the persistent v3 kernel when it applies (bf16, max_len <= 512)
-    const bool use_v3 = std::is_same<T, bf16>::value && attention_v3_ok(max_len, H);
-    if (!use_v3) launch_vt_cols(d_cu, n_docs, (int)M, e->vcol.as<int32_t>(), s);
-    for (size_t l = 0; l < e->layers.size(); ++l) {
-        Layer &L = *e->layers[l];
-        const bool last = l + 1 == e->layers.size();
-        GemmArgs g{};
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.hidden = H;
-        // QKV projection + attention.  bf16 with max_len <= 320: row-major [M][3H]
-        // and the persistent LDS-DMA attention (v3); otherwise Q|K row-major with V
-        // written transposed (doc-aligned V^T) for the generic attention kernels.
-        if (use_v3) {
-            g.A = X;
-            g.B = L.w_qkv.p;
-            g.bias = L.b_qkv.as<float>();
-            g.out = e->qk.p;
-            g.N = 3 * H;
-            g.K = H;
-            g.ld_out = 3 * H;
-            {
-                TimedLaunch tl(e->timer, timing, "gemm_qkv", s);
-                launch_gemm<T>(EPI_BIAS, g, s);
-            }
-            {
-                TimedLaunch tl(e->timer, timing, "attention", s);
-                launch_attention_v3(e->qk.as<bf16>(), d_cu, n_docs, max_len, H, e->ctx.as<bf16>(),
-                                    s);
-            }
-        } else {
-            g.A = X;
-            g.B = L.w_qkv.p;
-            g.bias = L.b_qkv.as<float>();
-            g.out = e->qk.p;
-            g.out2 = e->vt.p;
-            g.N = 3 * H;
-            g.K = H;
-            g.ld_out = 2 * H;
-            g.ld_v = e->ld_v;
-            g.vcol = e->vcol.as<int32_t>();
-            {
-                TimedLaunch tl(e->timer, timing, "gemm_qkv", s);
-                launch_gemm<T>(EPI_QKV, g, s);
-            }
-            if constexpr (std::is_same<T, float>::value)
-                pair_attn_layer(e, d_cu, n_docs, timing, s);
-            {
-                TimedLaunch tl(e->timer, timing, "attention", s);
-                launch_attention<T>(e->qk.as<T>(), e->vt.as<T>(), d_cu, n_docs, max_len, H,
-                                    e->ld_v, e->ctx.as<T>(), s);
-            }
-        }
-        // attention output + residual -> LN1 (fused into the GEMM when it can be)
-        g = GemmArgs{};
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.A = e->ctx.p;
-        g.B = L.w_o.p;
-        g.bias = L.b_o.as<float>();
-        g.resid = X;
-        g.out = e->pre.p;
-        g.N = H;
-        g.K = H;
-        g.ld_out = H;
-        g.ln_eps = c.layer_norm_eps;
-        {
-            TimedLaunch tl(e->timer, timing, "gemm_o", s);
-            launch_gemm<T>(EPI_BIAS_RESID, g, s);
-        }
-        {
-            TimedLaunch tl(e->timer, timing, "ln", s);
-            launch_ln<T>(e->pre.as<T>(), (int)M, H, L.ln1_g.as<float>(), L.ln1_b.as<float>(),
-                         c.layer_norm_eps, X1, nullptr, 0.f, c.activation, nullptr, s);
-        }
-        // FFN
-        g = GemmArgs{};
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.A = X1;
-        g.B = L.w_i.p;
-        g.bias = L.b_i.as<float>();
-        g.out = e->Hff.p;
-        g.N = F;
-        g.K = H;
-        g.ld_out = F;
-        {
-            TimedLaunch tl(e->timer, timing, "gemm_ffn1", s);
-            launch_gemm<T>(EPI_BIAS_GELU, g, s);
-        }
-        // FFN output + residual -> LN2; the last LayerNorm feeds only the impact head
-        g = GemmArgs{};
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.A = e->Hff.p;
-        g.B = L.w_out.p;
-        g.bias = L.b_out.as<float>();
-        g.resid = X1;
-        g.out = e->pre.p;
-        g.N = H;
-        g.K = F;
-        g.ld_out = H;
-        g.ln_eps = c.layer_norm_eps;
-        {
-            TimedLaunch tl(e->timer, timing, "gemm_ffn2", s);
-            launch_gemm<T>(EPI_BIAS_RESID, g, s);
-        }
-        {
-            TimedLaunch tl(e->timer, timing, "ln", s);
-            launch_ln<T>(e->pre.as<T>(), (int)M, H, L.ln2_g.as<float>(), L.ln2_b.as<float>(),
-                         c.layer_norm_eps, last ? nullptr : X,
-                         last ? e->head_w.as<float>() : nullptr, e->head_b, c.activation,
-                         last ? e->impact.as<float>() : nullptr, s);
-        }
-    }
+// One projection's GemmArgs: the forward's base (a_rows, hidden, tune_gm, split; folded:
+// stats_ld) with the projection's rows and operands.  What only its epilogue reads (the
+// residual, V^T, the LayerNorm folding parameters) the caller adds.
+GemmArgs proj(const GemmArgs &base, int64_t M, const void *A, const DevBuf &w, const float *bias,
+              void *out, int N, int K, int ld_out) {
+    GemmArgs g = base;
+    g.M = (int)M;
+    g.A = A;
+    g.B = w.p;
+    g.bias = bias;
+    g.out = out;
+    g.N = N;
+    g.K = K;
+    g.ld_out = ld_out;
+    return g;
 }
 
 // bf16 / bf16x3 forward with every LayerNorm after the embeddings folded into its consumers
@@ -482,21 +368,14 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
         else
             launch_gemm<bf16>(epi, g, s);
     };
-    auto base = [&]() {
-        GemmArgs g{};
-        // tile-order group: 8 M-tiles (measured +4% QKV, +1% O / FFN1 over 4); FFN2
-        // (K = 3072, N = 768) keeps 4
-        g.tune_gm = 8;
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.hidden = H;
-        g.stats_ld = ld;
-        g.n_part = n_part;
-        g.ln_h = H;
-        g.ln_eps = c.layer_norm_eps;
-        g.split = sp ? 1 : 0;
-        return g;
-    };
+    GemmArgs base{};
+    // tile-order group: 8 M-tiles (measured +4% QKV, +1% O / FFN1 over 4); FFN2
+    // (K = 3072, N = 768) keeps 4
+    base.tune_gm = 8;
+    base.a_rows = e->cap_rows;
+    base.hidden = H;
+    base.stats_ld = ld;
+    base.split = sp ? 1 : 0;
     for (size_t l = 0; l < e->layers.size(); ++l) {
         Layer &L = *e->layers[l];
         const Layer *P = l > 0 ? e->layers[l - 1].get() : nullptr;
@@ -520,14 +399,8 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
         const bool qc = prune && sp;
         if (qc) gather_rows();
         // QKV: layer 0 reads the normalised embeddings; later layers fold LN2(l-1)
-        GemmArgs g = base();
-        g.A = X;
-        g.B = L.w_qkv.p;
-        g.bias = L.b_qkv.as<float>();
-        g.out = e->qk.p;
-        g.N = 3 * H;
-        g.K = H;
-        g.ld_out = 3 * H * W2;
+        GemmArgs g = proj(base, M, X, L.w_qkv, L.b_qkv.as<float>(), e->qk.p, 3 * H, H,
+                          3 * H * W2);
         if (P) {
             g.row_ln = rl2;
             g.col_s = L.s_qkv.as<float>();
@@ -572,21 +445,9 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
                                     prune ? d_ct : nullptr);
         }
         if (prune && !qc) gather_rows();
-        auto base_r = [&]() {
-            GemmArgs gr = base();
-            gr.M = (int)Mr;
-            return gr;
-        };
         // O: P1 = ctx W_o^T + b_o + LN2(l-1)(X)  (plain X on layer 0) -> X1, stats1
-        g = base_r();
-        g.A = e->ctx.p;
-        g.B = L.w_o.p;
-        g.bias = L.b_o.as<float>();
+        g = proj(base, Mr, e->ctx.p, L.w_o, L.b_o.as<float>(), X1, H, H, H * W2);
         g.resid = Xr;
-        g.out = X1;
-        g.N = H;
-        g.K = H;
-        g.ld_out = H * W2;
         g.stats_out = st1;
         if (P) {
             g.row_ln = rl2r;
@@ -602,13 +463,8 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
             launch_row_ln(st1, ld, n_part, (int)Mr, H, c.layer_norm_eps, rl1, s);
         }
         // FFN1 on LN1(P1), folded
-        g = base_r();
-        g.A = X1;
-        g.B = L.w_i.p;
-        g.out = e->Hff.p;
-        g.N = F;
-        g.K = H;
-        g.ld_out = F * W2;
+        // (no bias: the folded epilogues carry it inside col_c)
+        g = proj(base, Mr, X1, L.w_i, nullptr, e->Hff.p, F, H, F * W2);
         g.row_ln = rl1;
         g.col_s = L.s_i.as<float>();
         g.col_c = L.c_i.as<float>();
@@ -617,15 +473,8 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
             gemm(EPI_FOLD_GELU, g);
         }
         // FFN2: P2 = Hff W_out^T + b_out + LN1(P1) -> X, stats2 (+ head dot, last layer)
-        g = base_r();
-        g.A = e->Hff.p;
-        g.B = L.w_out.p;
-        g.bias = L.b_out.as<float>();
+        g = proj(base, Mr, e->Hff.p, L.w_out, L.b_out.as<float>(), X, H, F, H * W2);
         g.resid = X1;
-        g.out = X;
-        g.N = H;
-        g.K = F;
-        g.ld_out = H * W2;
         g.tune_gm = 4;
         g.row_ln = rl1;
         g.res_gamma = L.ln1_g.as<float>();
@@ -649,125 +498,134 @@ void forward_folded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, in
     }
 }
 
-// fp32-faithful forward (DI_PREC_BF16X3): the unfolded post-LN structure of
-// forward<T> with every GEMM a split-bf16 256-tile GEMM (3 bf16 MFMA products per
-// fp32 product, f32 accumulate: ~2^-17 relative per product), attention with split
-// bf16 products too (attention_x3_kernel; f32 softmax), LayerNorms in f32 from f32
-// pre-LN rows.  Activations that feed a GEMM or the attention products are split
-// rows (Q | K and V^T included); the pre-LN rows are f32.
-// Pruned last layer (d_tt != nullptr), as forward_folded: after the last QKV projection
-// only the terms' first-token rows are computed (attention queries, O / FFN GEMMs,
-// LayerNorms, head), packed -- the same arithmetic per kept row, bit-identical impacts.
-void forward_split(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_docs,
-                   int64_t M, int max_len, bool timing, hipStream_t s,
-                   const int32_t *d_tt = nullptr, const int32_t *d_ct = nullptr,
-                   int64_t n_terms = 0) {
+// The unfolded post-LN forward (every LayerNorm its own pass), in three modes:
+//   FWD_FP32    f32 activations, weights and GEMMs.
+//   FWD_BF16    bf16 throughout (bf16 whose shapes the folding does not take, DI_NO_LN_FOLD).
+//   FWD_BF16X3  fp32-faithful (DI_PREC_BF16X3): every GEMM a split-bf16 256-tile GEMM (3 bf16
+//     MFMA products per fp32 product, f32 accumulate: ~2^-17 relative per product),
+//     attention with split bf16 products too (attention_x3_kernel; f32 softmax),
+//     LayerNorms in f32 from f32 pre-LN rows.  Activations that feed a GEMM or the
+//     attention products are split rows (Q | K | V included); the pre-LN rows are f32.
+// Pruned last layer (d_tt != nullptr; FWD_BF16X3 only), as forward_folded: after the last
+// QKV projection only the terms' first-token rows are computed (attention queries, O / FFN
+// GEMMs, LayerNorms, head), packed -- the same arithmetic per kept row, bit-identical impacts.
+enum FwdMode { FWD_FP32, FWD_BF16, FWD_BF16X3 };
+template <FwdMode MODE>
+void forward_unfolded(di_encoder *e, const int32_t *d_ids, const int32_t *d_cu, int n_docs,
+                      int64_t M, int max_len, bool timing, hipStream_t s,
+                      const int32_t *d_tt = nullptr, const int32_t *d_ct = nullptr,
+                      int64_t n_terms = 0) {
+    constexpr bool X3 = MODE == FWD_BF16X3;
+    using T = std::conditional_t<MODE == FWD_FP32, float, bf16>;    // activations, weights
+    using TP = std::conditional_t<MODE == FWD_BF16, bf16, float>;   // pre-LN rows
     const auto &c = e->cfg;
     const int H = c.hidden, F = c.intermediate;
     const int pos_offset = (c.variant == DI_VARIANT_XLMR) ? c.pad_id + 1 : 0;
-    bf16 *X = e->X.as<bf16>(), *X1 = e->X1.as<bf16>(), *ctx = e->ctx.as<bf16>();
-    float *pre = e->pre.as<float>();
+    DI_REQUIRE(X3 || !d_tt, DI_EINVAL, "pruned last layer: bf16x3 only");
+    T *X = e->X.as<T>(), *X1 = e->X1.as<T>();
+    TP *pre = e->pre.as<TP>();
     {
         TimedLaunch tl(e->timer, timing, "embed_ln", s);
-        launch_embed_ln_split(d_ids, d_cu, n_docs, (int)M, H, e->word.as<float>(),
-                              e->pos.as<float>(), e->type0.as<float>(), e->emb_g.as<float>(),
-                              e->emb_b.as<float>(), c.layer_norm_eps, pos_offset, c.vocab_size,
-                              c.max_positions, X, e->err.as<int32_t>(), s);
+        if constexpr (X3)
+            launch_embed_ln_split(d_ids, d_cu, n_docs, (int)M, H, e->word.as<float>(),
+                                  e->pos.as<float>(), e->type0.as<float>(), e->emb_g.as<float>(),
+                                  e->emb_b.as<float>(), c.layer_norm_eps, pos_offset,
+                                  c.vocab_size, c.max_positions, X, e->err.as<int32_t>(), s);
+        else
+            launch_embed_ln<T>(d_ids, d_cu, n_docs, (int)M, H, e->word.as<T>(), e->pos.as<T>(),
+                               e->type0.as<T>(), e->emb_g.as<float>(), e->emb_b.as<float>(),
+                               c.layer_norm_eps, pos_offset, c.vocab_size, c.max_positions, X,
+                               e->err.as<int32_t>(), s);
     }
-    auto base = [&]() {
-        GemmArgs g{};
-        g.M = (int)M;
-        g.a_rows = e->cap_rows;
-        g.hidden = H;
-        g.tune_gm = 8;
-        g.split = 1;
-        return g;
+    // QKV layout and attention.  bf16x3: split rows [M][6H] and attention_x3.  bf16 with
+    // max_len <= 512: row-major [M][3H] and the persistent LDS-DMA attention (v3).
+    // Otherwise Q|K row-major with V written transposed (doc-aligned V^T, EPI_QKV) for the
+    // generic attention kernels.
+    const bool use_v3 = MODE == FWD_BF16 && attention_v3_ok(max_len, H);
+    const bool vt = !X3 && !use_v3;
+    if (vt) launch_vt_cols(d_cu, n_docs, (int)M, e->vcol.as<int32_t>(), s);
+    auto gemm = [&](int epi, const GemmArgs &g) {
+        if constexpr (X3)
+            launch_gemm256(epi, g, s);
+        else
+            launch_gemm<T>(epi, g, s);
     };
+    auto ln = [&](int64_t rows, const DevBuf &gamma, const DevBuf &beta, T *out, bool head) {
+        TimedLaunch tl(e->timer, timing, "ln", s);
+        const float *hw = head ? e->head_w.as<float>() : nullptr;
+        float *impact = head ? e->impact.as<float>() : nullptr;
+        if constexpr (X3)
+            launch_ln_split(pre, (int)rows, H, gamma.as<float>(), beta.as<float>(),
+                            c.layer_norm_eps, out, hw, e->head_b, c.activation, impact, s);
+        else
+            launch_ln<T>(pre, (int)rows, H, gamma.as<float>(), beta.as<float>(),
+                         c.layer_norm_eps, out, hw, e->head_b, c.activation, impact, s);
+    };
+    GemmArgs base{};
+    base.a_rows = e->cap_rows;
+    base.hidden = H;
+    base.tune_gm = X3 ? 8 : 0;  // (tile-order group of the split GEMMs, see forward_folded)
+    base.split = X3 ? 1 : 0;
+    const int W2 = X3 ? 2 : 1;  // split rows: row stride 2W
     for (size_t l = 0; l < e->layers.size(); ++l) {
         Layer &L = *e->layers[l];
         const bool last = l + 1 == e->layers.size();
-        GemmArgs g = base();
-        g.A = X;
-        g.B = L.w_qkv.p;
-        g.bias = L.b_qkv.as<float>();
-        g.out = e->qk.p;  // split Q | K | V rows [M][6H]
-        g.N = 3 * H;
-        g.K = H;
-        g.ld_out = 6 * H;
+        const bool prune = last && d_tt != nullptr;
+        const int64_t Mr = prune ? n_terms : M;  // rows after the attention
+        GemmArgs g = proj(base, M, X, L.w_qkv, L.b_qkv.as<float>(), e->qk.p, 3 * H, H,
+                          X3 ? 6 * H : use_v3 ? 3 * H : 2 * H);
+        if (vt) {
+            g.out2 = e->vt.p;
+            g.ld_v = e->ld_v;
+            g.vcol = e->vcol.as<int32_t>();
+        }
         {
             TimedLaunch tl(e->timer, timing, "gemm_qkv", s);
-            launch_gemm256(EPI_BIAS, g, s);
+            gemm(vt ? EPI_QKV : EPI_BIAS, g);
         }
-        const bool prune = last && d_tt != nullptr;
-        const int64_t Mr = prune ? n_terms : M;  // rows from here on
-        bf16 *Xr = X;                             // the O GEMM's residual rows
-        pair_attn_layer(e, d_cu, n_docs, timing, s);
+        if constexpr (MODE != FWD_BF16) pair_attn_layer(e, d_cu, n_docs, timing, s);
         {
             TimedLaunch tl(e->timer, timing, "attention", s);
-            launch_attention_x3(e->qk.as<bf16>(), d_cu, n_docs, H, ctx, s,
-                                prune ? d_tt : nullptr, prune ? d_ct : nullptr, &e->aq);
+            if constexpr (X3)
+                launch_attention_x3(e->qk.as<bf16>(), d_cu, n_docs, H, e->ctx.as<bf16>(), s,
+                                    prune ? d_tt : nullptr, prune ? d_ct : nullptr, &e->aq);
+            else if (use_v3)
+                launch_attention_v3(e->qk.as<bf16>(), d_cu, n_docs, max_len, H, e->ctx.as<bf16>(),
+                                    s);
+            else
+                launch_attention<T>(e->qk.as<T>(), e->vt.as<T>(), d_cu, n_docs, max_len, H,
+                                    e->ld_v, e->ctx.as<T>(), s);
         }
+        T *Xr = X;  // the O GEMM's residual rows
         if (prune) {  // the terms' residual rows, packed into Hff (free until FFN1)
             TimedLaunch tl(e->timer, timing, "gather_rows", s);
-            Xr = e->Hff.as<bf16>();
-            launch_gather_term_rows(X, nullptr, d_cu, d_ct, d_tt, n_docs, 2 * H, Xr, nullptr, s);
+            Xr = e->Hff.as<T>();
+            launch_gather_term_rows(e->X.as<bf16>(), nullptr, d_cu, d_ct, d_tt, n_docs, 2 * H,
+                                    e->Hff.as<bf16>(), nullptr, s);
         }
-        auto base_r = [&]() {
-            GemmArgs gr = base();
-            gr.M = (int)Mr;
-            return gr;
-        };
-        g = base_r();
-        g.A = ctx;
-        g.B = L.w_o.p;
-        g.bias = L.b_o.as<float>();
+        // attention output + residual -> LN1
+        g = proj(base, Mr, e->ctx.p, L.w_o, L.b_o.as<float>(), pre, H, H, H);
         g.resid = Xr;
-        g.out = pre;
-        g.N = H;
-        g.K = H;
-        g.ld_out = H;
         {
             TimedLaunch tl(e->timer, timing, "gemm_o", s);
-            launch_gemm256(EPI_BIAS_RESID, g, s);
+            gemm(EPI_BIAS_RESID, g);
         }
-        {
-            TimedLaunch tl(e->timer, timing, "ln", s);
-            launch_ln_split(pre, (int)Mr, H, L.ln1_g.as<float>(), L.ln1_b.as<float>(),
-                            c.layer_norm_eps, X1, nullptr, 0.f, c.activation, nullptr, s);
-        }
-        g = base_r();
-        g.A = X1;
-        g.B = L.w_i.p;
-        g.bias = L.b_i.as<float>();
-        g.out = e->Hff.p;
-        g.N = F;
-        g.K = H;
-        g.ld_out = 2 * F;
+        ln(Mr, L.ln1_g, L.ln1_b, X1, false);
+        // FFN
+        g = proj(base, Mr, X1, L.w_i, L.b_i.as<float>(), e->Hff.p, F, H, F * W2);
         {
             TimedLaunch tl(e->timer, timing, "gemm_ffn1", s);
-            launch_gemm256(EPI_BIAS_GELU, g, s);
+            gemm(EPI_BIAS_GELU, g);
         }
-        g = base_r();
-        g.A = e->Hff.p;
-        g.B = L.w_out.p;
-        g.bias = L.b_out.as<float>();
+        // FFN output + residual -> LN2; the last LayerNorm feeds only the impact head
+        g = proj(base, Mr, e->Hff.p, L.w_out, L.b_out.as<float>(), pre, H, F, H);
         g.resid = X1;
-        g.out = pre;
-        g.N = H;
-        g.K = F;
-        g.ld_out = H;
-        g.tune_gm = 4;
+        if (X3) g.tune_gm = 4;
         {
             TimedLaunch tl(e->timer, timing, "gemm_ffn2", s);
-            launch_gemm256(EPI_BIAS_RESID, g, s);
+            gemm(EPI_BIAS_RESID, g);
         }
-        {
-            TimedLaunch tl(e->timer, timing, "ln", s);
-            launch_ln_split(pre, (int)Mr, H, L.ln2_g.as<float>(), L.ln2_b.as<float>(),
-                            c.layer_norm_eps, last ? nullptr : X,
-                            last ? e->head_w.as<float>() : nullptr, e->head_b, c.activation,
-                            last ? e->impact.as<float>() : nullptr, s);
-        }
+        ln(Mr, L.ln2_g, L.ln2_b, last ? nullptr : X, last);
     }
 }
 
@@ -898,20 +756,17 @@ void encode_impl(di_encoder *e, const int32_t *tok_ids, const int32_t *cu_seqlen
     const bool prune = !token_out && (e->split || (e->esz == 2 && e->folded)) &&
                        n_terms <= n_tokens;  // (packed term rows fit the row buffers)
     if (n_tokens > 0) {
-        if (e->split && !e->folded)
-            forward_split(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
-                          prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
-        else if (e->split)
+        if (e->folded)  // (bf16 and bf16x3 only, di_encoder_create)
             forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
                            prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
+        else if (e->split)
+            forward_unfolded<FWD_BF16X3>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
+                                         prune ? d_tt : nullptr, prune ? d_cut : nullptr,
+                                         n_terms);
         else if (e->esz == 2)
-            if (e->folded)
-                forward_folded(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s,
-                               prune ? d_tt : nullptr, prune ? d_cut : nullptr, n_terms);
-            else
-                forward<bf16>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
+            forward_unfolded<FWD_BF16>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
         else
-            forward<float>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
+            forward_unfolded<FWD_FP32>(e, d_ids, d_cu, n_docs, n_tokens, max_len, timing, s);
     }
     float *d_out = out;
     DevBuf tmp;
