@@ -6,8 +6,8 @@
 
 namespace di {
 
-// The layout constants the builder shares with the scorer (index.hip asserts they are its
-// own MAX_BLOCK_DOCS, WSEG, WLONG_MIN and POST_X).
+// The layout constants the builder shares with the scorer (index.hip asserts they are
+// index_score.h's MAX_BLOCK_DOCS, WSEG, WLONG_MIN and POST_X).
 constexpr int IL_BLOCK_DOCS = 32768;
 constexpr int IL_WSEG = 16;
 constexpr int IL_WLONG_MIN = 128;

@@ -30,6 +30,7 @@
 
 #include "sparse_common.h"
 #include "topk_common.h"
+#include "topk_merge.h"
 
 namespace di {
 
@@ -404,17 +405,10 @@ sparse_merge64_kernel(const Key96 *__restrict__ cand, const int32_t *__restrict_
     if (tid == 0) out_n[q] = n;
 }
 
-void launch_merge(const uint64_t *keys, const int32_t *counts, int n_q, int n_lists, int k_in,
-                  int k, uint64_t *out_key, uint32_t *out_doc, uint32_t *out_score,
-                  int32_t *out_n, int mode, hipStream_t s, bool lists_major,
-                  const int32_t *cu_q);
-void enable_big_lds();
-
 void sparse_init(di_sparse &sp, int device) {
     sp.device = device;
     DI_HIP(hipStreamCreateWithFlags(&sp.stream, hipStreamNonBlocking));
     sp.own_stream = true;
-    enable_big_lds();
     DI_HIP(hipFuncSetAttribute((const void *)sparse_score_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)sizeof(SparseShared)));
@@ -554,7 +548,7 @@ int di_sparse_search(di_sparse *sp, const uint32_t *q_terms, const int32_t *cu_q
             TimedLaunch tl(sp->timer, timing, "merge_topk", s);
             launch_merge(sp->ws_ck.as<uint64_t>(), sp->ws_cn.as<int32_t>(), nq, nb, k, k,
                          key.d ? key.d + (int64_t)q0 * k : nullptr, doc.d + (int64_t)q0 * k,
-                         sc.d + (int64_t)q0 * k, on.d + q0, 1 /*DECODE_SPARSE*/, s, false, nullptr);
+                         sc.d + (int64_t)q0 * k, on.d + q0, DECODE_SPARSE, s, false, nullptr);
         }
         doc.copy_back(s);
         sc.copy_back(s);

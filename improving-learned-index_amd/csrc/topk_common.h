@@ -145,4 +145,29 @@ __device__ __forceinline__ void bitonic_sort_desc(uint64_t *s, int n) {
     }
 }
 
+// Wave-aggregated append: lanes with `take` get consecutive slots of *cursor (one
+// LDS atomic per wave and call).  Call from wave-uniform control flow.
+// MB: the leader's base by v_readlane and the lanes below by v_mbcnt -- no LDS permute
+// and no lane mask held in registers (the block-max instantiation spilled a held 64-bit
+// mask and reloaded it per sweep step: 74 -> 8 scratch loads, its sweep 2x faster); the
+// plain scorer keeps the permute form (measured 2.06 vs 2.09 ms per 100 k-doc launch).
+template <bool MB = false>
+__device__ __forceinline__ bool wave_append(bool take, uint32_t *cursor, uint32_t &pos) {
+    const uint64_t m = __ballot(take);
+    if (m == 0) return false;
+    const int lane = threadIdx.x & 63;
+    const int leader = __builtin_ctzll(m);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(cursor, (uint32_t)__builtin_popcountll(m));
+    if constexpr (MB) {
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+        pos = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                               __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    } else {
+        base = __shfl(base, leader, 64);
+        pos = base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    }
+    return take;
+}
+
 }  // namespace di

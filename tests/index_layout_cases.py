@@ -11,7 +11,7 @@ import functools
 
 import numpy as np
 
-MAX_BLOCK_DOCS = 32768   # csrc/index.hip
+MAX_BLOCK_DOCS = 32768   # csrc/index_score.h
 WSEG = 16
 WLONG_MIN = 128
 POST_X = MAX_BLOCK_DOCS << 10

@@ -6,7 +6,7 @@ import functools
 
 import numpy as np
 
-# csrc/index.hip: the constants launch_merge and the merge kernels branch on
+# csrc/topk_merge.hip: the constants launch_merge and the merge kernels branch on
 MS_LISTS = 64          # merge_sel_kernel: at most this many lists
 MS_THREADS = 512       # ... with 8 or 16 candidates per thread
 MG_SEL_MIN = 1024      # counting selection only above this many candidates
@@ -143,7 +143,7 @@ def _in_bins_at_or_above_take(bins, take, total):
 
 def expected_path(n_lists, k, counts_of_query, any_key_ge_2_60, bins=None):
     """The kernel and the branches one query takes, "kernel/load/selection", restating
-    csrc/index.hip: launch_merge (the dispatch on n_lists, k and the LDS capacity `cap`,
+    csrc/topk_merge.hip: launch_merge (the dispatch on n_lists, k and the LDS capacity `cap`,
     "few short lists" to the three launches), merge_sel_kernel (`counting`, `n_sel <=
     MG_SEL_KEYS`, `take < total`) and merge_topk_kernel (`fast_lists`, `total <= cap`, the
     two-pass filter's `big` and `n_keep <= cap`, `if (over)`, and the selection's condition

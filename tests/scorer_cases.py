@@ -1,6 +1,6 @@
 """Shared inputs of tests/test_scorer_cases_cpu.py and tests/test_scorer_edges_gpu.py (not a
 test module): constructed collections and queries for the quantized-index scorer
-(score_blocks_kernel / score_long_kernel / item_setup_kernel of csrc/index.hip), the numpy
+(score_blocks_kernel / score_long_kernel / item_setup_kernel of csrc/index_score.hip), the numpy
 definition of its accumulator words and of the exact top-k, and a restatement of which
 selection route and which scatter rounds a (query, block) item takes, so that the CPU test
 can prove that the GPU cases between them reach every route and every round shape.
@@ -11,7 +11,7 @@ import functools
 
 import numpy as np
 
-# csrc/index.hip: the constants the scorer branches on
+# csrc/index_score.h / index_score.hip: the constants the scorer branches on
 MAX_BLOCK_DOCS = 32768        # docs per block (one workgroup's LDS accumulators)
 SC_THREADS = 1024             # threads per workgroup; all-wave rounds are multiples of it
 WSEG = 16                     # wave segments per block (SC_THREADS / 64)

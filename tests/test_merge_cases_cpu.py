@@ -1,6 +1,6 @@
 """The cases of tests/test_topk_merge_gpu.py, checked without a GPU: every case takes the
 route of di_topk_merge that its row names (merge_cases.expected_path restates the dispatch
-of csrc/index.hip), the cases between them take every route, the numpy definition agrees
+of csrc/topk_merge.hip), the cases between them take every route, the numpy definition agrees
 with Python's sorted(), and the data tells the two list layouts apart."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""di_topk_merge called directly on every route of launch_merge (csrc/index.hip): the cases
+"""di_topk_merge called directly on every route of launch_merge (csrc/topk_merge.hip): the cases
 of tests/merge_cases.py (tests/test_merge_cases_cpu.py proves that they reach every kernel
 and branch), each in the query-major and the lists-major layout, on host pointers and on
 device pointers with DI_F_ASYNC on a torch stream -- the call parallel._exchange_merge
