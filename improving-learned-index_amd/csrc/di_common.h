@@ -7,11 +7,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <thread>
@@ -272,6 +274,30 @@ inline void check_launch(const char *what) {
         set_error("launch of %s failed: %s", what, hipGetErrorString(e));
         throw Error{DI_EHIP};
     }
+}
+
+// A kernel that takes more than 64 KiB of dynamic LDS must opt in
+// (hipFuncAttributeMaxDynamicSharedMemorySize): once per kernel and device, not per launch.
+// `set_on` is the call site's static for `kernels`, one bit per device (a device past 63
+// sets the limit at every call).
+struct DynLds {
+    const void *kern;
+    int bytes;
+};
+inline void dynamic_lds_once(std::atomic<uint64_t> &set_on, std::initializer_list<DynLds> kernels) {
+    int dev = 0;
+    DI_HIP(hipGetDevice(&dev));
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (set_on.load(std::memory_order_acquire) & bit) return;
+    int lds_max = 0;
+    DI_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    for (const DynLds &k : kernels) {
+        DI_REQUIRE(k.bytes <= lds_max, DI_ERANGE,
+                   "a kernel needs %d bytes of LDS per workgroup, device %d has %d", k.bytes, dev,
+                   lds_max);
+        DI_HIP(hipFuncSetAttribute(k.kern, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
+    }
+    set_on.fetch_or(bit, std::memory_order_release);
 }
 
 // The current device set to `dev` for a scope, and put back after it.

@@ -18,11 +18,9 @@
 
 #include "di_common.h"
 #include "enc_common.h"
+#include "enc_launch.h"
 
 namespace di {
-
-bool gemm256_ok(int epi, const GemmArgs &g);
-void launch_gemm256(int epi, const GemmArgs &g, hipStream_t s);
 
 constexpr int GB_M = 128, GB_N = 128, G_THREADS = 256;
 constexpr int ROW_BYTES = 128;                 // bytes of one row per K step

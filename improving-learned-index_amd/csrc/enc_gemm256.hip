@@ -45,6 +45,7 @@
 
 #include "di_common.h"
 #include "enc_common.h"
+#include "enc_launch.h"
 
 namespace di {
 
@@ -755,14 +756,7 @@ void launch_gemm256(int epi, const GemmArgs &g, hipStream_t s) {
     DI_REQUIRE(kern, DI_EINVAL, "gemm256: bad%s GEMM epilogue %d", sp ? " split" : "", epi);
     // the dynamic LDS limit: once per instantiation and device, not per launch
     static std::atomic<uint64_t> set_on[2][8];
-    int dev = 0;
-    DI_HIP(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-    if (!(set_on[sp][epi].load(std::memory_order_acquire) & bit)) {
-        DI_HIP(hipFuncSetAttribute((const void *)kern,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS));
-        set_on[sp][epi].fetch_or(bit, std::memory_order_release);
-    }
+    dynamic_lds_once(set_on[sp][epi], {{(const void *)kern, G2_LDS}});
     hipLaunchKernelGGL(kern, grid, dim3(G2_T), G2_LDS, s, g);
     check_launch(sp ? "gemm256_split" : "gemm256");
 }

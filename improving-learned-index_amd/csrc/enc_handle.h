@@ -34,11 +34,6 @@ struct AttnQueue {
 };
 constexpr int AQ_CTL = 5, AQ_LONG = 0, AQ_SHORT = 1, AQ_ALL = 3;  // ctl index of a slice's [lo, hi)
 constexpr int AQ_LONG_LEN = 192;  // one pass of the 4-wave form
-// the knob DI_ATTN_X3_QUEUE (developer A/B): 0 no list, 1 one launch per layer, 2 two forms
-int attn_queue_mode();
-bool attn_order_ok(int max_positions);
-void launch_attn_order(const int32_t *cu_seqlens, int n_docs, int max_positions, int32_t *order,
-                       int32_t *ctl, hipStream_t s);
 
 }  // namespace di
 

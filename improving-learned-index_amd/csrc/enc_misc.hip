@@ -9,6 +9,7 @@
 
 #include "di_common.h"
 #include "enc_common.h"
+#include "enc_launch.h"
 
 namespace di {
 

@@ -1692,24 +1692,12 @@ namespace {
 // Kernels using more than 64 KiB of dynamic LDS must opt in: once per process and device.
 void enable_score_lds() {
     static std::atomic<uint64_t> set_on{0};
-    int dev = 0;
-    DI_HIP(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-    if (set_on.load(std::memory_order_acquire) & bit) return;
-    int lds_max = 0;
-    DI_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-    DI_REQUIRE((int)sizeof(ScoreShared) <= lds_max, DI_ERANGE,
-               "the scorer needs %zu bytes of LDS per workgroup, device %d has %d",
-               sizeof(ScoreShared), dev, lds_max);
-    const void *kernels[] = {(const void *)score_blocks_kernel<0>,
-                             (const void *)score_blocks_kernel<EXT_BM>,
-                             (const void *)score_blocks_kernel<EXT_FEW>,
-                             (const void *)score_blocks_kernel<EXT_PK>,
-                             (const void *)score_long_kernel};
-    for (const void *kern : kernels)
-        DI_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)sizeof(ScoreShared)));
-    set_on.fetch_or(bit, std::memory_order_release);
+    constexpr int LDS = (int)sizeof(ScoreShared);
+    dynamic_lds_once(set_on, {{(const void *)score_blocks_kernel<0>, LDS},
+                              {(const void *)score_blocks_kernel<EXT_BM>, LDS},
+                              {(const void *)score_blocks_kernel<EXT_FEW>, LDS},
+                              {(const void *)score_blocks_kernel<EXT_PK>, LDS},
+                              {(const void *)score_long_kernel, LDS}});
 }
 
 }  // namespace

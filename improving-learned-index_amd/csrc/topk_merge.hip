@@ -527,23 +527,12 @@ merge_sel_kernel(const uint64_t *__restrict__ keys, const int32_t *__restrict__ 
 // Kernels using more than 64 KiB of dynamic LDS must opt in: once per process and device.
 static void enable_merge_lds() {
     static std::atomic<uint64_t> set_on{0};
-    int dev = 0;
-    DI_HIP(hipGetDevice(&dev));
-    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
-    if (set_on.load(std::memory_order_acquire) & bit) return;
-    DI_HIP(hipFuncSetAttribute((const void *)merge_topk_kernel<256>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(MergeHead<256>) + MG_LDS_KEYS * 8)));
-    DI_HIP(hipFuncSetAttribute((const void *)merge_topk_kernel<512>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(MergeHead<512>) + MG_LDS_KEYS * 8)));
-    DI_HIP(hipFuncSetAttribute((const void *)merge_sel_kernel<512, 16>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(MergeSelHead<512>) + MG_SEL_KEYS * 8)));
-    DI_HIP(hipFuncSetAttribute((const void *)merge_sel_kernel<512>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)(sizeof(MergeSelHead<512>) + MG_SEL_KEYS * 8)));
-    set_on.fetch_or(bit, std::memory_order_release);
+    dynamic_lds_once(
+        set_on,
+        {{(const void *)merge_topk_kernel<256>, (int)(sizeof(MergeHead<256>) + MG_LDS_KEYS * 8)},
+         {(const void *)merge_topk_kernel<512>, (int)(sizeof(MergeHead<512>) + MG_LDS_KEYS * 8)},
+         {(const void *)merge_sel_kernel<512, 16>, (int)(sizeof(MergeSelHead<512>) + MG_SEL_KEYS * 8)},
+         {(const void *)merge_sel_kernel<512>, (int)(sizeof(MergeSelHead<512>) + MG_SEL_KEYS * 8)}});
 }
 
 void launch_merge(const uint64_t *keys, const int32_t *counts, int n_q, int n_lists, int k_in,

@@ -19,7 +19,8 @@ CSRC = ROOT / "improving-learned-index_amd" / "csrc"
 
 @pytest.mark.skipif(not Path(asm_wait_scan.HIPCC).exists() and shutil.which("hipcc") is None,
                     reason="hipcc not available")
-@pytest.mark.parametrize("src", ["enc_attn.hip", "enc_gemm256.hip", "enc_gemm.hip", "enc_misc.hip",
+@pytest.mark.parametrize("src", ["enc_attn.hip", "enc_attn_v3.hip", "enc_attn_x3.hip",
+                                 "enc_gemm256.hip", "enc_gemm.hip", "enc_misc.hip",
                                  "encoder.hip", "index_score.hip", "sparse.hip"])
 def test_no_early_use_of_asm_lds_reads(src):
     text = asm_wait_scan.compile_asm(CSRC / src)

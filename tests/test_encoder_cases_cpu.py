@@ -3,7 +3,7 @@ proved from the CPU oracle alone (oracle/encoder_ref.py; no GPU).
 
 With seeded_state_dict(std 0.02) weights the attention logits stay under ~2, so no softmax
 row of any existing encoder test moves the device's lazy reference maximum after the first
-key chunk (enc_attn.hip soft_a: rescale when a score passes the reference by 8 in base 2),
+key chunk (enc_attn_x3.hip soft_a: rescale when a score passes the reference by 8 in base 2),
 and shifting K by one head moves the impacts by about the suite's 1e-3 bound.  The
 peaked_state_dict weights of tests/encoder_cases.py (logit standard deviation 6, value /
 output projections doubled) are held to three conditions here, for every (shape, lens) the

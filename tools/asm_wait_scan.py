@@ -10,7 +10,7 @@ that touches a destination register of an inline-asm ds_read (global / buffer
 load) before the next lgkmcnt (vmcnt) wait, and every inline-asm instruction that
 touches an MFMA result within the MFMA -> VALU hazard window (scan_mfma_asm_reads).
 
-    python tools/asm_wait_scan.py improving-learned-index_amd/csrc/enc_attn.hip
+    python tools/asm_wait_scan.py improving-learned-index_amd/csrc/enc_attn_x3.hip
 """
 import re
 import subprocess

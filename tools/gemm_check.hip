@@ -13,12 +13,8 @@
 #include <vector>
 
 #include "../improving-learned-index_amd/csrc/enc_common.h"
+#include "../improving-learned-index_amd/csrc/enc_launch.h"
 
-namespace di {
-template <typename T>
-void launch_gemm(int epi, const GemmArgs &g, hipStream_t s);
-void launch_gemm256(int epi, const GemmArgs &g, hipStream_t s);
-}
 using namespace di;
 
 #define CK(x)                                                                  \
